@@ -8,6 +8,10 @@ one process per GPU over RCCL (weak scaling: SF100 shard per GPU = one part of
 SF 100*N), plus the partial-state exchange leg (BASELINE config 4 shape).
 
 Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--sf-per-gpu S]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line. --full adds the legs that take runs of their own (the CPU baseline).
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 Driver launches N>1 via torch.distributed.run; reads RANK/WORLD_SIZE/etc.
 """
 import argparse
@@ -88,6 +92,32 @@ def combo_owner_rank(combo, world):
     return (lh * world) >> 32
 
 
+Q1_F64_FIELDS = ("sum_qty", "sum_base", "sum_disc_price", "sum_charge",
+                 "avg_qty", "avg_price", "avg_disc", "sum_disc")
+
+
+def _u64_words(vals):
+    """u64 accumulator words as an [n, 2] float64 array of (low, high) 32-bit
+    halves: every value is exact in float64."""
+    import numpy as np
+    return np.array([[v & 0xFFFFFFFF, v >> 32] for v in vals], dtype=np.float64)
+
+
+def dump_q1_outputs(dirpath, res, merged=None):
+    """Write the Q1Result a caller of the timed path receives (and, at N>1,
+    this rank's merged exchange state) as DIR/<name>.npy, float64."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    for f in Q1_F64_FIELDS:
+        np.save(os.path.join(dirpath, f + ".npy"),
+                np.array(list(getattr(res, f)), dtype=np.float64))
+    np.save(os.path.join(dirpath, "count.npy"),
+            np.array(list(res.count), dtype=np.float64))
+    np.save(os.path.join(dirpath, "raw.npy"), _u64_words(list(res.raw)))
+    if merged is not None:
+        np.save(os.path.join(dirpath, "merged_raw.npy"), _u64_words(merged))
+
+
 def main():
     # this libomp's first parallel region costs ~2.5 s when OMP_NUM_THREADS
     # is unset (measured; 0.4 s with it set) — pin the default before the
@@ -102,10 +132,22 @@ def main():
     ap.add_argument("--workload", choices=["q1", "q3", "sweep", "parquet"],
                     default="q1")
     ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure "
+                         "(the host-core CPU baseline of the q1 workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo only for multi-rank validation on one GPU "
                          "(RCCL requires distinct devices per rank)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.workload == "sweep":
+        ap.error("--dump-outputs is not available for --workload sweep")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -201,10 +243,14 @@ def main():
     k_ms = sum(kernel_ms) / len(kernel_ms)
     achieved_gbps = rows_rank * ALG_BYTES_PER_ROW / (k_ms / 1000.0) / 1e9
 
-    # ---- CPU baseline (rank 0, N=1 only): the parity-pinned oracle timed on
-    # host cores over a bounded sample (SF1 = 6,001,215 rows, repeated) ----
+    if args.dump_outputs and rank == 0:
+        dump_q1_outputs(args.dump_outputs, res, merged)
+
+    # ---- CPU baseline (--full; rank 0, N=1 only): the parity-pinned oracle
+    # timed on host cores over a bounded sample (SF1 = 6,001,215 rows,
+    # repeated) ----
     cpu_baseline = None
-    if rank == 0 and n_gpus == 1 and not args.skip_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.skip_cpu_baseline:
         import oracle
         cores = os.cpu_count() or 1
         li = oracle.gen_lineitem(1.0)
@@ -341,6 +387,11 @@ def run_q3(args, sess, n_gpus, rank, tdist=None):
         r["top10"] = tgdist.merge_topn(tdist, r["top10"], 10,
                                        key=lambda t: (-t[1], t[2]))
     tpch_queries.q3_release(sess, inp)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "top10.npy"),
+                np.array(r["top10"], dtype=np.float64).reshape(-1, 4))
     ms = elapsed * 1000 / args.steps
     value = rows / (elapsed / args.steps)
     out = {
@@ -523,18 +574,20 @@ def run_parquet(args, sess, n_gpus, rank):
         for k in d:
             setattr(cols, k, d[k])
         r = sess.q1(cols)
-        return time.time() - t0, t_dec, t_up, r.elapsed_ms
+        return time.time() - t0, t_dec, t_up, r
 
     for _ in range(max(args.warmup, 1)):
         step()
     t_start = time.time()
     tot_dec = tot_up = tot_k = 0.0
     for _ in range(args.steps):
-        el, t_dec, t_up, k_ms = step()
+        el, t_dec, t_up, res = step()
         tot_dec += t_dec
         tot_up += t_up
-        tot_k += k_ms / 1000.0
+        tot_k += res.elapsed_ms / 1000.0
     elapsed = time.time() - t_start
+    if args.dump_outputs and rank == 0:
+        dump_q1_outputs(args.dump_outputs, res)
     ms = elapsed * 1000 / args.steps
     raw = n * 38
     out_rec = {
