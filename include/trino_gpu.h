@@ -170,7 +170,10 @@ typedef struct tg_agg_spec {
     /* masked aggregation (AggregationMask analog, predicate form): the row
      * contributes to THIS aggregate only when col[mask_gt_a] > col[mask_gt_b]
      * (filter clause lowered into the accumulator; -1 = unmasked). Lets one
-     * pass compute filtered and unfiltered aggregates side by side. */
+     * pass compute filtered and unfiltered aggregates side by side. A NULL
+     * in either mask cell fails the gate. Mask channels are integer/date
+     * typed: a DOUBLE or VARCHAR mask channel makes add_input return
+     * TG_ERR_UNSUPPORTED (channel types arrive with the first page). */
     int32_t mask_gt_a;
     int32_t mask_gt_b;
     int32_t _pad;
@@ -403,7 +406,12 @@ tg_status tg_mark_distinct_create(tg_session*, const int32_t* key_channels,
 /* dense-range single-BIGINT-key aggregation (direct array state, one
  * atomic per row — or an atomic pair for the 128-bit exact sum; groups
  * emit in key order). For COUNT/SUM_I64/SUM_F64_EXACT over keys with
- * known dense statistics (generated custkeys/suppkeys). */
+ * known dense statistics (generated custkeys/suppkeys).
+ * Contract: every non-NULL key in [key_min, key_max] that occurs in the
+ * input is emitted as a group, also when its aggregate is 0 (a SUM that
+ * cancels, a COUNT_COL over only NULL values). Rows whose key is NULL or
+ * outside [key_min, key_max] are DROPPED silently — unlike a hash
+ * aggregation, which would group them; the caller guarantees the range. */
 tg_status tg_dense_aggregation_create(tg_session*, int32_t key_channel,
     int64_t key_min, int64_t key_max, const tg_agg_spec* agg, tg_operator**);
 

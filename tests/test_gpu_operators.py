@@ -1583,6 +1583,26 @@ class TestAdaptivePartialAgg:
             ctrl.attach(op)
         op.close()
         ctrl.close()
+        # DOUBLE mask channel (either side of the gate): rejected with
+        # TG_ERR_UNSUPPORTED on the first page, where channel types are
+        # known — hash and streaming; an integer pair is still accepted
+        k = np.arange(8, dtype=np.int64)
+        v = np.arange(8, dtype=np.int64)
+        d = np.linspace(-1.0, 1.0, 8)
+        i = np.arange(8, dtype=np.int32)
+        page = ops.page_from_numpy([k, v, d, i])
+        for ma, mb, ok in ((2, 3, False), (3, 2, False), (3, 1, True)):
+            spec = [(ops.AGG_SUM_I64, 1, 0, ma, mb)]
+            for op in (ops.hash_aggregation(sess, [0], [ops.TG_BIGINT], spec),
+                       ops.streaming_aggregation(sess, 0, spec)):
+                if ok:
+                    op.add_input(page)
+                    assert len(op.drain()[0][0]["values"]) == 8
+                else:
+                    with pytest.raises(trino_amd.TrinoGpuError) as ei:
+                        op.add_input(page)
+                    assert str(ei.value).startswith("status 6:")  # TG_ERR_UNSUPPORTED
+                op.close()
 
 
 class TestDedupSort:

@@ -175,3 +175,169 @@ class TestJoin:
         assert s[0] == 1.5 + 2.5 + -1.0 and s[1] == 5.0
         c = oracle.grouped_count(gids, 2)
         assert list(c) == [3, 2]
+
+
+class TestAggregationMatrixHost:
+    """Host-side checks for tests/test_gpu_aggregation_matrix.py: the key
+    shape constructors reach the k_agg_update path their docstrings name
+    (CPU simulation of the per-wave choice), the streaming shapes have the
+    run ends they claim, and the module's reference matches hand-computed
+    answers. No GPU, no oracle."""
+
+    @staticmethod
+    def mx():
+        import test_gpu_aggregation_matrix as m
+        return m
+
+    @pytest.mark.parametrize("shape", ["uniform", "hot2", "hot8", "hot_then_tail",
+                                       "bail", "interleaved", "scatter", "single"])
+    def test_shape_reaches_named_path(self, shape):
+        m = self.mx()
+        assert set(m.SHAPES) == set(m.SHAPE_PATHS)
+        assert m.SHAPES[shape].__doc__
+        for n in m.SMALL_NS + (64 * 7,):
+            g = m.SHAPES[shape](n)
+            assert len(g) == n
+            # distinct group indexes map to distinct keys
+            assert len(set(m.key_of(g).tolist())) == len(set(g.tolist()))
+            full = n // 64
+            for s in range(full):
+                assert m.simulate_wave(g[s * 64:(s + 1) * 64]) == m.SHAPE_PATHS[shape]
+            if n % 64:     # partial last wave never takes the uniform path
+                assert m.simulate_wave(g[full * 64:])["path"] == "hot"
+        g = m.SHAPES[shape](1000)
+        if shape == "uniform":
+            assert all(g[s * 64] != g[(s + 1) * 64] for s in range(14))
+        if shape == "interleaved":
+            assert g[0] == g[2] != g[1] == g[3]
+
+    def test_simulation_counts(self):
+        m = self.mx()
+        # 9 clusters of 7 + one lane: small first cluster bails after round 1
+        assert m.simulate_wave([i // 7 for i in range(64)]) == dict(
+            path="hot", exit="bail", rounds=1, first=7, leftover=57)
+        # 9 groups, first of 8 lanes: 8 rounds, the ninth group is left over
+        g = [i // 8 for i in range(56)] + [7] * 4 + [8] * 4
+        assert m.simulate_wave(g) == dict(path="hot", exit="rounds8", rounds=8,
+                                          first=8, leftover=4)
+        # 64 equal ids but only 63 active lanes: not uniform
+        assert m.simulate_wave([3] * 63) == dict(path="hot", exit="drained",
+                                                 rounds=1, first=63, leftover=0)
+
+    def test_streaming_shapes(self):
+        m = self.mx()
+
+        def end_lanes(name, n=1000):
+            g = m.runs_to_gids(m.STREAM_SHAPES[name], n)
+            assert len(g) == n and np.all(np.diff(g) >= 0)
+            ends = np.flatnonzero(np.diff(g)) % 64
+            return g, set(ends.tolist())
+
+        g, ends = end_lanes("runs1")
+        assert len(set(g.tolist())) == 1000
+        g, ends = end_lanes("runs63_64_65")
+        assert np.bincount(g)[:3].tolist() == [63, 64, 65]
+        g, ends = end_lanes("run200")
+        assert 200 in np.bincount(g).tolist()
+        g, ends = end_lanes("ends62_63_0")
+        assert ends == {62, 63, 0}
+        assert m.GRID_STRIDE_N == 524_288 + 64 * 3 + 5
+
+    def test_value_patterns(self):
+        m = self.mx()
+        from fractions import Fraction
+        gid = np.asarray(m.SHAPES["hot2"](1000), np.int64)
+        iv, fv, ew, em = m.value_cols(gid, 1)
+        for c in (iv, fv, ew, em):
+            assert 0.2 < 1 - c.valid.mean() < 0.4          # ~30 % NULLs
+            assert c.valid[m.first_rows(gid)].all()
+        assert iv.values[iv.valid].min() < -2 ** 38 and iv.values[iv.valid].max() > 2 ** 38
+        m.assert_exact_precondition(ew.values[ew.valid], m.SP_WIDE)
+        m.assert_exact_precondition(em.values[em.valid], m.SP_MONEY)
+        with pytest.raises(AssertionError):
+            m.assert_exact_precondition(np.array([0.1]), 20)
+        with pytest.raises(AssertionError):
+            m.assert_exact_precondition(np.array([2.0 ** 44]), 20)
+        sums = []
+        for g in sorted(set(gid.tolist())):
+            sel = (gid == g) & ew.valid
+            sums.append(sum(Fraction(x) for x in ew.values[sel].tolist()))
+        scaled = [s * 2 ** m.SP_WIDE for s in sums]
+        assert any(abs(s) >= 2 ** 64 for s in scaled)        # crosses 2^64
+        assert any(s > 0 for s in scaled) and any(s < 0 for s in scaled)
+        assert any(Fraction(float(s)) != s for s in sums)    # > 53 bits: rounds
+
+    def test_reference_tiny_ints_and_nulls(self):
+        m = self.mx()
+        k = m.Col(np.array([7, -2, 7, -2, 7, 9], np.int64))
+        v = m.Col(np.array([5, 1, -8, m.POISON_I, 3, m.POISON_I], np.int64),
+                  [1, 1, 1, 0, 1, 0])
+        aggs = [m.Agg(m.COUNT_STAR), m.Agg(m.COUNT_COL, 1), m.Agg(m.SUM_I64, 1),
+                m.Agg(m.MIN_I64, 1), m.Agg(m.MAX_I64, 1)]
+        r = m.reference([k, v], [0], aggs)
+        assert r.keys == [(7,), (-2,), (9,)]            # first-occurrence order
+        assert r.cols == [[3, 2, 1], [3, 1, 0], [0, 1, None],
+                          [-8, 1, None], [5, 1, None]]
+        assert r.sizes == [3, 2, 1]
+        with pytest.raises(AssertionError):
+            m.assert_sums_defined(r, aggs)
+        # wraparound: Python's sum reduced mod 2^64
+        w = m.reference([m.Col(np.zeros(2, np.int64)),
+                         m.Col(np.array([2 ** 62 + 5, 2 ** 62 + 7], np.int64))],
+                        [0], [m.Agg(m.SUM_I64, 1)])
+        assert w.cols == [[-2 ** 63 + 12]]
+
+    def test_reference_tiny_mask_and_two_channel_key(self):
+        m = self.mx()
+        k1 = m.Col(np.array([1, 1, 1, 2, 2, 1], np.int64))
+        k2 = m.Col(np.array([0, 5, 0, 5, 5, 0], np.int32), [1, 1, 1, 1, 1, 0])
+        v = m.Col(np.array([10, 20, 30, 40, 50, 60], np.int64))
+        a = m.Col(np.array([3, -1, 9, -4, -9, 9], np.int32), [1, 1, 0, 1, 1, 1])
+        b = m.Col(np.array([-3, -2, 0, -4, -8, 8], np.int64))
+        aggs = [m.Agg(m.COUNT_STAR, -1, 0, (3, 4)), m.Agg(m.SUM_I64, 2, 0, (3, 4)),
+                m.Agg(m.MIN_I64, 2, 0, (3, 4)), m.Agg(m.MAX_I64, 2)]
+        r = m.reference([k1, k2, v, a, b], [0, 1], aggs)
+        # groups: (1,0) rows 0,2; (1,5) row 1; (2,5) rows 3,4; (1,NULL) row 5
+        assert r.keys == [(1, 0), (1, 5), (2, 5), (1, None)]
+        # gate a > b: row0 yes, row1 yes, row2 NULL a -> no, row3 -4 > -4 no,
+        # row4 -9 > -8 no, row5 yes; group (2,5) is masked out entirely
+        assert r.cols == [[1, 1, 0, 1], [10, 20, None, 60],
+                          [10, 20, None, 60], [30, 20, 50, 60]]
+        assert aggs[0].spec() == (m.COUNT_STAR, -1, 0, 3, 4)
+        assert aggs[3].spec() == (m.MAX_I64, 2, 0)
+
+    def test_reference_tiny_doubles(self):
+        m = self.mx()
+        from fractions import Fraction
+        k = m.Col(np.array([4, 4, 4, 6, 6], np.int64))
+        big = 2.0 ** 60
+        v = m.Col(np.array([big, 1.0, -big, 0.5, np.nan]), [1, 1, 1, 1, 0])
+        aggs = [m.Agg(m.SUM_F64_EXACT, 1, 1), m.Agg(m.SUM_F64, 1), m.Agg(m.AVG_F64, 1)]
+        r = m.reference([k, v], [0], aggs)
+        assert r.keys == [(4,), (6,)]
+        assert r.cols[0] == [1.0, 0.5]          # exact: cancellation keeps the 1
+        assert r.cols[0][0] == float(Fraction(big) + 1 - Fraction(big))
+        assert r.cols[1] == [1.0, 0.5]
+        assert r.cols[2] == [1.0 / 3.0, 0.5]
+        # bounds: n_g * 2^-53 * sum|v|; AVG: that / count + 2^-53 * |avg|
+        assert r.bounds[0] is None
+        assert r.bounds[1] == [3 * 2.0 ** -53 * (2 * big + 1), 2 * 2.0 ** -53 * 0.5]
+        assert r.bounds[2] == [r.bounds[1][0] / 3 + 2.0 ** -53 / 3.0,
+                               r.bounds[1][1] / 1 + 2.0 ** -53 * 0.5]
+        # scalar aggregation of nothing: one group, COUNT 0, AVG NULL
+        e = m.reference([m.Col(np.zeros(0, np.int64)), m.Col(np.zeros(0))], [],
+                        [m.Agg(m.COUNT_STAR), m.Agg(m.AVG_F64, 1)])
+        assert e.keys == [()] and e.cols == [[0], [None]]
+
+    def test_validity_packing_and_dense_reference(self):
+        m = self.mx()
+        v = np.arange(130) % 3 != 0
+        w = m.pack_valid(v)
+        assert len(w) == 3 and int(w[0]) & 0b111 == 0b110
+        assert np.array_equal(m.unpack_valid(w, 130), v)
+        assert m.unpack_valid(None, 5).all()
+        k = m.Col(np.array([5, 2, 9, 2, 5, 2], np.int32), [1, 1, 1, 1, 0, 1])
+        x = m.Col(np.array([4, 1, 7, -1, 8, m.POISON_I], np.int64), [1, 1, 1, 1, 1, 0])
+        r = m.dense_reference([k, x], 2, 5, m.Agg(m.SUM_I64, 1))
+        # key 9 out of range, row 4 NULL key; key 2 sums to 0 and is a group
+        assert sorted(zip(r.keys, r.cols[0])) == [((2,), 0), ((5,), 4)]

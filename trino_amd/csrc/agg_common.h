@@ -16,6 +16,11 @@ struct KAgg {
 };
 #define MAX_AGGS 12
 
+/* rejects mask channels that are out of range (TG_ERR_INVALID_ARG) or
+ * DOUBLE/VARCHAR (TG_ERR_UNSUPPORTED); checked per input page */
+tg_status agg_check_mask_channels(const DevPage& in,
+                                  const std::vector<tg_agg_spec>& aggs);
+
 __global__ void k_agg_update(const int32_t* gids, int64_t n,
                              const KColH* cols, const KAgg* aggs, int n_aggs,
                              int step);
@@ -28,7 +33,8 @@ __global__ void k_emit_i64(const long long* state, const int32_t* old_by_new,
                            int32_t n, int64_t* out);
 __global__ void k_emit_i64_biased(const long long* state,
                                   const int32_t* old_by_new, int32_t n,
-                                  int64_t* out);
+                                  int64_t* out, unsigned long long identity,
+                                  uint64_t* out_valid);
 __global__ void k_emit_avg(const double* sum, const long long* cnt,
                            const int32_t* old_by_new, int32_t n, double* out,
                            uint64_t* out_valid);

@@ -232,8 +232,11 @@ __global__ void k_agg_update(const int32_t* __restrict__ gids, int64_t n,
             bool row_ok = active;
             if (active && ag.mask_a >= 0 && ag.mask_a != ag.mask_b) {
                 /* masked aggregate: col[mask_a] > col[mask_b] gates the row
-                 * (typed: both int32 or int64 supported via kcol_word) */
-                row_ok = kcol_sval(cols[ag.mask_a], i) >
+                 * (typed: both int32 or int64 supported via kcol_word); a
+                 * NULL operand makes the comparison not true (SQL) */
+                row_ok = !kcol_is_null(cols[ag.mask_a], i) &&
+                         !kcol_is_null(cols[ag.mask_b], i) &&
+                         kcol_sval(cols[ag.mask_a], i) >
                          kcol_sval(cols[ag.mask_b], i);
             }
             /* per-lane addend for this agg */
@@ -485,7 +488,9 @@ __global__ void k_agg_update_sorted(const int32_t* __restrict__ gids, int64_t n,
                       : (ag.fn == TG_AGG_MAX_I64) ? 2 : 0;
             bool row_ok = active;
             if (active && ag.mask_a >= 0 && ag.mask_a != ag.mask_b) {
-                row_ok = kcol_sval(cols[ag.mask_a], i) >
+                row_ok = !kcol_is_null(cols[ag.mask_a], i) &&
+                         !kcol_is_null(cols[ag.mask_b], i) &&
+                         kcol_sval(cols[ag.mask_a], i) >
                          kcol_sval(cols[ag.mask_b], i);
             }
             long long ci = mmode == 1 ? INT64_MAX
@@ -693,14 +698,25 @@ __global__ void k_emit_f64(const double* __restrict__ state, const int32_t* old_
     if (g < n) out[g] = state[old_by_new[g]];
 }
 
+/* MIN/MAX emit. With out_valid (SINGLE/FINAL steps) a state that still
+ * equals the biased identity means no non-NULL row qualified: the cell is
+ * SQL NULL. A genuine INT64_MAX minimum (INT64_MIN maximum) has the same
+ * state and is therefore reported as NULL too. PARTIAL
+ * output passes out_valid = nullptr and keeps the plain identity value, so
+ * FINAL combines it unchanged. */
 __global__ void k_emit_i64_biased(const long long* __restrict__ state,
                                   const int32_t* __restrict__ old_by_new,
-                                  int32_t n, int64_t* __restrict__ out)
+                                  int32_t n, int64_t* __restrict__ out,
+                                  unsigned long long identity,
+                                  uint64_t* __restrict__ out_valid)
 {
     int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
-    out[g] = (int64_t)((unsigned long long)state[old_by_new ? old_by_new[g] : g]
-                       ^ 0x8000000000000000ull);
+    unsigned long long st =
+        (unsigned long long)state[old_by_new ? old_by_new[g] : g];
+    out[g] = (int64_t)(st ^ 0x8000000000000000ull);
+    if (out_valid && st == identity)
+        atomicAnd((unsigned long long*)&out_valid[g >> 6], ~(1ull << (g & 63)));
 }
 
 __global__ void k_emit_i64(const long long* __restrict__ state, const int32_t* old_by_new,
@@ -841,6 +857,31 @@ __global__ void k_pa_state(const KColH* __restrict__ cols, int64_t n, KAgg ag,
                 break;
         }
     }
+}
+
+/* mask gates compare integer views (kcol_sval): DOUBLE words are canonical
+ * bit patterns (wrong order for negatives) and VARCHAR has no word at all.
+ * Input channel types are known only once a page arrives, so both
+ * aggregation operators call this on every add_input. */
+tg_status agg_check_mask_channels(const DevPage& in,
+                                  const std::vector<tg_agg_spec>& aggs)
+{
+    for (const tg_agg_spec& a : aggs) {
+        if (a.mask_gt_a < 0 || a.mask_gt_a == a.mask_gt_b) continue;
+        for (int32_t ch : {a.mask_gt_a, a.mask_gt_b}) {
+            if (ch < 0 || ch >= (int32_t)in.blocks.size()) {
+                TG_SET_ERR("masked aggregate: mask channel %d out of range", ch);
+                return TG_ERR_INVALID_ARG;
+            }
+            tg_type ty = in.blocks[ch].type;
+            if (ty == TG_DOUBLE || ty == TG_VARCHAR) {
+                TG_SET_ERR("masked aggregate: mask channel %d must be an "
+                           "integer/date type (DOUBLE/VARCHAR unsupported)", ch);
+                return TG_ERR_UNSUPPORTED;
+            }
+        }
+    }
+    return TG_OK;
 }
 
 struct HashAggOp : tg_operator {
@@ -1048,6 +1089,8 @@ struct HashAggOp : tg_operator {
         DevPage in;
         tg_status st = tg_upload_page(s, page, &in);
         if (st != TG_OK) return st;
+        st = agg_check_mask_channels(in, aggs);
+        if (st != TG_OK) { tg_free_page(s, &in); return st; }
         if (pa && step == TG_STEP_PARTIAL) {
             if (pa->disabled.load(std::memory_order_relaxed))
                 return pass_through(std::move(in));
@@ -1177,6 +1220,12 @@ have_gids:;
          * partial states are already staged; no hash-table output page */
         if (passed_through && !group_channels.empty() && ng == 0)
             return TG_OK;
+        /* scalar aggregation (AggregationOperator) emits exactly one row even
+         * when no page arrived: the freshly initialised state of group 0
+         * (COUNT 0, SUM 0, MIN/MAX/AVG NULL). PARTIAL emits nothing; its
+         * FINAL then takes this path. */
+        if (group_channels.empty() && ng == 0 && step != TG_STEP_PARTIAL)
+            ng = 1;
         /* remap: order groups by first-occurrence row (== the reference's
          * insertion-order ids, deterministically) */
         int32_t* d_obn = nullptr;
@@ -1281,11 +1330,18 @@ have_gids:;
             }
             else if (ag.fn == TG_AGG_MIN_I64 || ag.fn == TG_AGG_MAX_I64) {
                 /* state is sign-bit-biased u64; emit the plain int64 value
-                   (PARTIAL and FINAL states are identical) */
+                   (PARTIAL and FINAL states are identical). SINGLE/FINAL
+                   mark groups with no qualifying row NULL. */
                 DevBlock b; b.type = TG_BIGINT; b.n = ng;
                 TG_POOL_ALLOC(s, &b.data, (int64_t)(ng ? ng : 1) * 8);
+                if (final_out) {
+                    int64_t words = (ng + 63) / 64;
+                    TG_POOL_ALLOC(s, &b.valid, (words ? words : 1) * 8);
+                    TG_HIP_CHECK(hipMemsetAsync(b.valid, 0xFF, words * 8, s->stream));
+                }
                 hipLaunchKernelGGL(k_emit_i64_biased, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                                   ag.cnt, d_obn, ng, (int64_t*)b.data);
+                                   ag.cnt, d_obn, ng, (int64_t*)b.data,
+                                   ag.fn == TG_AGG_MIN_I64 ? ~0ull : 0ull, b.valid);
                 outp.blocks.push_back(b);
             }
             else if (ag.fn == TG_AGG_SUM_F64) {
@@ -1415,10 +1471,22 @@ extern "C" tg_status tg_hash_aggregation_create(tg_session* s,
  * one atomic per row, no probes, no keystore. A hardware-first variant of
  * BigintGroupByHash for the planner's "key statistics known" case; output
  * groups emit in KEY order (SQL-level parity: pipelines re-order anyway).
- * COUNT_STAR / COUNT_COL / SUM_I64 only (the use cases are count shapes). */
+ * COUNT_STAR / COUNT_COL / SUM_I64 / SUM_F64_EXACT. Every non-NULL key in
+ * [key_min, key_max] that occurs is a group, whatever its aggregate value;
+ * NULL keys and keys outside the range are dropped. */
+
+/* presence is tracked apart from the state (a touched key whose SUM is 0,
+ * whose exact sum cancels or whose COUNT_COL saw only NULLs is still a
+ * group): one byte per key, set on the first non-NULL in-range key.
+ * Check-then-store keeps it a cached read once the byte is set. */
+__device__ static inline void dense_mark_present(uint8_t* present, int64_t k)
+{
+    if (!present[k]) present[k] = 1;
+}
 
 __global__ void k_dense_update(const KColH key, int64_t n, int64_t key_min,
                                int64_t range, long long* __restrict__ state,
+                               uint8_t* present,
                                const KColH val, int fn, double scale)
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1426,7 +1494,8 @@ __global__ void k_dense_update(const KColH key, int64_t n, int64_t key_min,
     for (; i < n; i += stride) {
         if (kcol_is_null(key, i)) continue;
         int64_t k = (int64_t)kcol_word(key, i) - key_min;
-        if (k < 0 || k >= range) continue;   /* guarded (caller promises) */
+        if (k < 0 || k >= range) continue;   /* out-of-range keys are dropped */
+        dense_mark_present(present, k);
         if (fn == TG_AGG_SUM_F64_EXACT) {
             /* 128-bit fixed-point direct-array state (2 words per key):
              * same carry-propagating atomics as the hash/streaming paths */
@@ -1457,6 +1526,7 @@ __global__ void k_dense_update(const KColH key, int64_t n, int64_t key_min,
  * measured 25.3 ms with direct global atomics). */
 __global__ void k_dense_update_lds(const KColH key, int64_t n, int64_t key_min,
                                    int64_t range, long long* __restrict__ state,
+                                   uint8_t* present,
                                    const KColH val, int fn)
 {
     extern __shared__ long long h[];
@@ -1468,6 +1538,7 @@ __global__ void k_dense_update_lds(const KColH key, int64_t n, int64_t key_min,
         if (kcol_is_null(key, i)) continue;
         int64_t k = (int64_t)kcol_word(key, i) - key_min;
         if (k < 0 || k >= range) continue;
+        dense_mark_present(present, k);
         long long add = 1;
         if (fn == TG_AGG_SUM_I64 || fn == TG_AGG_COUNT_COL)
             add = (fn == TG_AGG_COUNT_COL)
@@ -1489,6 +1560,7 @@ __global__ void k_dense_update_lds(const KColH key, int64_t n, int64_t key_min,
 __global__ void k_dense_update_lds_exact(const KColH key, int64_t n,
                                          int64_t key_min, int64_t range,
                                          long long* __restrict__ state,
+                                         uint8_t* present,
                                          const KColH val, double scale)
 {
     extern __shared__ long long h[];   /* [2*range]: lo, hi interleaved */
@@ -1497,9 +1569,11 @@ __global__ void k_dense_update_lds_exact(const KColH key, int64_t n,
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        if (kcol_is_null(key, i) || kcol_is_null(val, i)) continue;
+        if (kcol_is_null(key, i)) continue;
         int64_t k = (int64_t)kcol_word(key, i) - key_min;
         if (k < 0 || k >= range) continue;
+        dense_mark_present(present, k);
+        if (kcol_is_null(val, i)) continue;
         double y = ((const double*)val.data)[i] * scale;
         __int128 yi = (__int128)(long long)y;
         unsigned long long lov = (unsigned long long)(unsigned __int128)yi;
@@ -1521,9 +1595,9 @@ __global__ void k_dense_update_lds_exact(const KColH key, int64_t n,
     }
 }
 
-__global__ void k_dense_present(const long long* __restrict__ state, int64_t range,
+__global__ void k_dense_present(const uint8_t* __restrict__ present, int64_t range,
                                 int32_t* __restrict__ chunk_counts, int64_t nchunks,
-                                int64_t chunk, int words)
+                                int64_t chunk)
 {
     int64_t c = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
     if (c >= nchunks) return;
@@ -1531,14 +1605,14 @@ __global__ void k_dense_present(const long long* __restrict__ state, int64_t ran
     int64_t lo = c * chunk, hi = min(lo + chunk, range);
     int32_t cnt = 0;
     for (int64_t i = lo + lane; i < hi; i += 64)
-        cnt += (state[i * words] != 0 ||
-                (words == 2 && state[i * words + 1] != 0));
+        cnt += present[i] != 0;
     #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
     if (lane == 0) chunk_counts[c] = cnt;
 }
 
-__global__ void k_dense_emit(const long long* __restrict__ state, int64_t range,
+__global__ void k_dense_emit(const long long* __restrict__ state,
+                             const uint8_t* __restrict__ present, int64_t range,
                              int64_t key_min, const int32_t* __restrict__ offs,
                              int64_t nchunks, int64_t chunk,
                              int64_t* __restrict__ out_keys,
@@ -1552,7 +1626,7 @@ __global__ void k_dense_emit(const long long* __restrict__ state, int64_t range,
     int32_t run = offs[c];
     for (int64_t g = lo; g < hi; g += 64) {
         int64_t i = g + lane;
-        bool p = (i < hi) && state[i] != 0;
+        bool p = (i < hi) && present[i] != 0;
         unsigned long long b = __ballot(p);
         int before = __popcll(b & ((1ull << lane) - 1ull));
         if (p) {
@@ -1565,6 +1639,7 @@ __global__ void k_dense_emit(const long long* __restrict__ state, int64_t range,
 
 /* exact-sum variant: 2-word state, emits the correctly-rounded double */
 __global__ void k_dense_emit_exact(const long long* __restrict__ state,
+                                   const uint8_t* __restrict__ present,
                                    int64_t range, int64_t key_min,
                                    const int32_t* __restrict__ offs,
                                    int64_t nchunks, int64_t chunk,
@@ -1580,7 +1655,7 @@ __global__ void k_dense_emit_exact(const long long* __restrict__ state,
     int32_t run = offs[c];
     for (int64_t g = lo; g < hi; g += 64) {
         int64_t i = g + lane;
-        bool p = (i < hi) && (state[2 * i] != 0 || state[2 * i + 1] != 0);
+        bool p = (i < hi) && present[i] != 0;
         unsigned long long b = __ballot(p);
         int before = __popcll(b & ((1ull << lane) - 1ull));
         if (p) {
@@ -1600,6 +1675,7 @@ struct DenseAggOp : tg_operator {
     int64_t key_min = 0, range = 0;
     tg_agg_spec agg{};
     long long* state = nullptr;
+    uint8_t* present = nullptr;   /* [range] 1 = key seen (non-NULL, in range) */
     double scale = 1.0;     /* SUM_F64_EXACT fixed-point scale (2^scale_pow) */
     int words = 1;          /* state words per key (2 for SUM_F64_EXACT) */
     bool emitted = false;
@@ -1621,17 +1697,17 @@ struct DenseAggOp : tg_operator {
             hipLaunchKernelGGL(k_dense_update_lds_exact,
                                dim3(tg_grid_for(in.n)), dim3(TG_BLOCK),
                                range * 16, s->stream, kc, in.n, key_min,
-                               range, state, vc, scale);
+                               range, state, present, vc, scale);
         }
         else if (range <= 8192 && words == 1) {
             hipLaunchKernelGGL(k_dense_update_lds, dim3(tg_grid_for(in.n)),
                                dim3(TG_BLOCK), range * 8, s->stream, kc, in.n,
-                               key_min, range, state, vc, agg.fn);
+                               key_min, range, state, present, vc, agg.fn);
         }
         else {
             hipLaunchKernelGGL(k_dense_update, dim3(tg_grid_for(in.n)),
                                dim3(TG_BLOCK), 0, s->stream, kc, in.n,
-                               key_min, range, state, vc, agg.fn, scale);
+                               key_min, range, state, present, vc, agg.fn, scale);
         }
         TG_HIP_CHECK(hipGetLastError());
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -1651,8 +1727,8 @@ struct DenseAggOp : tg_operator {
         int wpb = TG_BLOCK / 64;
         hipLaunchKernelGGL(k_dense_present,
                            dim3((uint32_t)((nchunks + wpb - 1) / wpb)),
-                           dim3(TG_BLOCK), 0, s->stream, state, range, d_offs,
-                           nchunks, CH, words);
+                           dim3(TG_BLOCK), 0, s->stream, present, range, d_offs,
+                           nchunks, CH);
         TG_HIP_CHECK(hipGetLastError());
         tg_status st = run_scan_i32(s, d_offs, nchunks, d_total);
         if (st != TG_OK) return st;
@@ -1670,14 +1746,14 @@ struct DenseAggOp : tg_operator {
         TG_POOL_ALLOC(s, &bv.data, (int64_t)(total ? total : 1) * 8);
         if (agg.fn == TG_AGG_SUM_F64_EXACT) {
             hipLaunchKernelGGL(k_dense_emit_exact, dim3((uint32_t)nchunks),
-                               dim3(64), 0, s->stream, state, range, key_min,
-                               d_offs, nchunks, CH, 1.0 / scale,
+                               dim3(64), 0, s->stream, state, present, range,
+                               key_min, d_offs, nchunks, CH, 1.0 / scale,
                                (int64_t*)bk.data, (double*)bv.data);
         }
         else {
             hipLaunchKernelGGL(k_dense_emit, dim3((uint32_t)nchunks), dim3(64),
-                               0, s->stream, state, range, key_min, d_offs,
-                               nchunks, CH, (int64_t*)bk.data,
+                               0, s->stream, state, present, range, key_min,
+                               d_offs, nchunks, CH, (int64_t*)bk.data,
                                (int64_t*)bv.data);
         }
         TG_HIP_CHECK(hipGetLastError());
@@ -1702,6 +1778,7 @@ struct DenseAggOp : tg_operator {
     ~DenseAggOp() override
     {
         if (state) tg_pool_free(s, state);
+        if (present) tg_pool_free(s, present);
         for (auto& p : out_pages_) tg_free_page(s, &p);
     }
 };
@@ -1734,7 +1811,12 @@ extern "C" tg_status tg_dense_aggregation_create(tg_session* s,
         delete op;
         return TG_ERR_OOM;
     }
+    if (tg_pool_alloc(s, (void**)&op->present, op->range) != TG_OK) {
+        delete op;
+        return TG_ERR_OOM;
+    }
     (void)hipMemsetAsync(op->state, 0, op->range * 8 * op->words, s->stream);
+    (void)hipMemsetAsync(op->present, 0, op->range, s->stream);
     (void)hipStreamSynchronize(s->stream);
     *out = op;
     return TG_OK;

@@ -119,6 +119,8 @@ struct StreamAggOp : tg_operator {
         DevPage in;
         tg_status st = tg_upload_page(s, page, &in);
         if (st != TG_OK) return st;
+        st = agg_check_mask_channels(in, aggs);
+        if (st != TG_OK) { tg_free_page(s, &in); return st; }
         if (in.n == 0) { tg_free_page(s, &in); return TG_OK; }
         const DevBlock& kb = in.blocks[key_channel];
         if (kb.type != TG_BIGINT || kb.valid) {
@@ -300,8 +302,14 @@ void StreamAggOp::st_emit_aggs(DevPage* outp, int64_t ng)
         else if (ag.fn == TG_AGG_MIN_I64 || ag.fn == TG_AGG_MAX_I64) {
             DevBlock b; b.type = TG_BIGINT; b.n = ng;
             (void)tg_pool_alloc(s, (void**)&b.data, (int64_t)(ng ? ng : 1) * 8);
+            if (final_out) {   /* no qualifying row => NULL (k_emit_i64_biased) */
+                int64_t words = (ng + 63) / 64;
+                (void)tg_pool_alloc(s, (void**)&b.valid, (words ? words : 1) * 8);
+                (void)hipMemsetAsync(b.valid, 0xFF, words * 8, s->stream);
+            }
             hipLaunchKernelGGL(k_emit_i64_biased, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                               ag.cnt, d_obn, (int32_t)ng, (int64_t*)b.data);
+                               ag.cnt, d_obn, (int32_t)ng, (int64_t*)b.data,
+                               ag.fn == TG_AGG_MIN_I64 ? ~0ull : 0ull, b.valid);
             outp->blocks.push_back(b);
         }
         else if (ag.fn == TG_AGG_SUM_F64) {
