@@ -203,7 +203,16 @@ tg_status tg_hash_builder_create(tg_session*, tg_join_bridge*,
     tg_operator** out);
 
 /* join_type: 0 = inner, 1 = probe-outer (LEFT: unmatched probe rows emit
- * one row with a NULL build side — LookupJoinOperators probe-outer) */
+ * one row with a NULL build side — LookupJoinOperators probe-outer; every
+ * build output column, VARCHAR included, carries a cleared validity bit).
+ * Output order: probe rows ascending, the build rows matching one probe row
+ * descending by global build row (reverse insertion).
+ * Key equality is SQL `=`: a key with a NULL component never matches;
+ * DOUBLE components compare with IEEE == (-0.0 matches 0.0, NaN matches
+ * nothing, itself included) — unlike grouping, where all NaNs are one key.
+ * The probe's key channels must equal the build's in count and, position by
+ * position, in type: add_input rejects anything else with
+ * TG_ERR_INVALID_ARG (channel types arrive with the first page). */
 tg_status tg_lookup_join_create_ex(tg_session*, tg_join_bridge*,
     const int32_t* probe_types, int32_t n_probe_channels,
     const int32_t* key_channels, int32_t n_key_channels,
@@ -442,7 +451,12 @@ tg_status tg_topn_create(tg_session*,
     int32_t limit, tg_operator** out);
 
 /* ---- semi join (operator/HashSemiJoinOperator.java): appends a BOOLEAN
- * matched channel to the probe page (NULL for null probe keys) ---- */
+ * matched channel to the probe page. Three-valued IN: a hit is true; a NULL
+ * probe key is false against a build of zero rows and NULL otherwise; a miss
+ * is NULL when the build holds a NULL key, else false. Same `=` as the
+ * lookup join (NaN matches nothing). One key channel: add_input rejects a
+ * bridge built on several key channels with TG_ERR_UNSUPPORTED, and a probe
+ * key whose type differs from the build key's with TG_ERR_INVALID_ARG. ---- */
 /* SetBuilderOperator analog (ChannelSet): semi-join membership source.
  * Dense single-BIGINT key ranges build a bitmap; sparse fall back to the
  * positional index. The bridge then serves tg_semi_join_create only. */

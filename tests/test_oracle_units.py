@@ -341,3 +341,254 @@ class TestAggregationMatrixHost:
         r = m.dense_reference([k, x], 2, 5, m.Agg(m.SUM_I64, 1))
         # key 9 out of range, row 4 NULL key; key 2 sums to 0 and is a group
         assert sorted(zip(r.keys, r.cols[0])) == [((2,), 0), ((5,), 4)]
+
+
+class TestJoinMatrixHost:
+    """Host-side checks for tests/test_gpu_join_matrix.py: its reference
+    gives hand-computed answers, the vectorised twin and the oracle's
+    independent join agree with it, every key shape constructor has the
+    property its docstring claims, and every size constant equals the value
+    derived from the constants parsed out of the sources. No GPU."""
+
+    @staticmethod
+    def mx():
+        import test_gpu_join_matrix as m
+        return m
+
+    def test_ref_join_by_hand(self):
+        m = self.mx()
+        nan = float("nan")
+        build = [(7,), (3,), (7,), (None,), (7,)]
+        probe = [(7,), (4,), (None,), (3,)]
+        # duplicates descending; NULL never matches; outer misses emit one row
+        assert m.ref_join(build, probe, False) == [(0, 4), (0, 2), (0, 0), (3, 1)]
+        assert m.ref_join(build, probe, True) == [
+            (0, 4), (0, 2), (0, 0), (1, None), (2, None), (3, 1)]
+        # a NULL in any component; integers by value
+        assert m.ref_join([(1, None), (1, 2), (None, 2)], [(1, 2), (1, None)],
+                          True) == [(0, 1), (1, None)]
+        # NaN matches nothing, not even the same object; -0.0 matches 0.0
+        assert m.ref_join([(nan,), (0.0,), (-0.0,)], [(nan,), (-0.0,), (0.0,)],
+                          True) == [(0, None), (1, 2), (1, 1), (2, 2), (2, 1)]
+        assert m.ref_join([(m.NAN_A,), (m.NAN_B,)], [(m.NAN_A,), (m.NAN_B,)],
+                          False) == []
+        # VARCHAR by bytes: '' is a value, not NULL
+        assert m.ref_join([(b"",), (b"a",), (None,)], [(b"",), (None,), (b"a\0",)],
+                          False) == [(0, 0)]
+        assert m.ref_join([], [(1,), (None,)], False) == []
+        assert m.ref_join([], [(1,), (None,)], True) == [(0, None), (1, None)]
+
+    def test_ref_semi_by_hand(self):
+        m = self.mx()
+        nan = float("nan")
+        assert m.ref_semi([(1,), (2,)], [(1,), (3,), (None,)]) == [True, False, None]
+        # a miss against a build that contains a NULL key is NULL; a hit stays True
+        assert m.ref_semi([(1,), (None,)], [(1,), (3,), (None,)]) == [True, None, None]
+        # NULL IN (empty) is False
+        assert m.ref_semi([], [(1,), (None,)]) == [False, False]
+        assert m.ref_semi([(nan,), (0.0,)], [(nan,), (-0.0,)]) == [False, True]
+        assert m.ref_semi([(nan,), (None,)], [(nan,)]) == [None]
+
+    def test_vectorised_twin_equals_ref_join(self):
+        m = self.mx()
+        r = np.random.default_rng(1)
+        for trial in range(40):
+            nb, mm = int(r.integers(0, 40)), int(r.integers(0, 40))
+            bk = r.integers(-4, 5, nb).astype(np.int64) * 2 ** 40
+            pk = r.integers(-5, 6, mm).astype(np.int64) * 2 ** 40
+            bv = r.random(nb) > 0.2 if trial % 3 else None
+            pv = r.random(mm) > 0.2 if trial % 2 else None
+            bkeys = [(int(k) if bv is None or bv[i] else None,) for i, k in enumerate(bk)]
+            pkeys = [(int(k) if pv is None or pv[i] else None,) for i, k in enumerate(pk)]
+            op, ob = m.ref_join_vec(bk, bv, pk, pv)
+            assert list(zip(op.tolist(), ob.tolist())) == m.ref_join(bkeys, pkeys, False)
+            hit, null = m.ref_semi_vec(bk, bv, pk, pv)
+            got = [None if z else bool(h) for h, z in zip(hit, null)]
+            assert got == m.ref_semi(bkeys, pkeys)
+
+    def test_ref_join_equals_oracle_join(self):
+        """two independent implementations, single BIGINT keys"""
+        m = self.mx()
+        for shape in ("unique", "dups", "nulls", "colliding", "one_hot"):
+            nb = 1000
+            bk, bnull, pk, pnull = m.SHAPES[shape](nb, 300, seed=3)
+            bvalid = None if bnull is None else m.pack_bits(~bnull)
+            pvalid = None if pnull is None else m.pack_bits(~pnull)
+            t = oracle.JoinTable(bk, valid=bvalid)
+            op, ob = t.probe(pk, probe_valid=pvalid, cap=10 ** 6)
+            build, probe = m.bigint_tables(bk, bnull, pk, pnull)
+            ref = m.ref_join(m.keys_of(build, [0]), m.keys_of(probe, [0]), False)
+            assert sorted(zip(op.tolist(), ob.tolist())) == sorted(ref)
+
+    def test_size_constants_follow_the_sources(self):
+        m = self.mx()
+        c = m.source_constants()
+        assert m.JREG_SLOTS == c["JREG_SLOTS"] and m.JSCAN_CHUNK == c["JSCAN_CHUNK"]
+        assert m.WAVE == 64
+        assert m.GRID_THREADS == c["TG_BLOCK"] * c["TG_MAX_BLOCKS"]
+        assert m.GRID_STRIDE_M > m.GRID_THREADS and m.GRID_STRIDE_M % 64 not in (0, 63)
+        (l1, f1), (l2, f2), (_, f3) = c["LOAD"]
+        assert (f1, f2, f3) == (0.25, 0.5, 0.75)
+        # region edge: the last build size with one region, the first with two
+        lo, hi = m.REGION_BUILDS
+        assert hi == lo + 1
+        assert m.join_hash_size(lo) == c["JREG_SLOTS"]
+        assert m.join_hash_size(hi) == 2 * c["JREG_SLOTS"]
+        # load-factor step
+        assert m.LOAD_BUILDS == (l1, l1 + 1)
+        assert m.join_hash_size(l1) == l1 * 4 and m.join_hash_size(l1 + 1) == l1 * 4
+        assert m.join_hash_size(l1 + 1) < (l1 + 1) * 4     # now half full at most
+        # the big build: second load-factor step, 64 regions, a second stride
+        # in every build kernel, and a table that is cut into two partitions
+        assert m.BIG_BUILD == l2 and m.join_hash_size(l2) == 2 * l2
+        assert m.join_hash_size(l2) // c["JREG_SLOTS"] == 64
+        assert m.BIG_BUILD > m.GRID_THREADS
+        tbl = m.join_hash_size(l2) * 4 + l2 * 12
+        assert c["PART_BYTES"] < tbl <= 2 * c["PART_BYTES"]
+        # probe page edges around the scan chunk: one, two and three chunks
+        ch = c["JSCAN_CHUNK"]
+        assert set(m.PROBE_EDGES) >= {1, 63, 64, 65, ch - 1, ch, ch + 1, 2 * ch + 1}
+        assert m.join_hash_size(0) == 2 and m.join_hash_size(1) == 4
+        for nb in m.SMALL_BUILDS:
+            assert m.join_hash_size(nb) <= c["JREG_SLOTS"]
+        # murmur3 restatement against this file's independent Python one
+        ks = np.array([0, 1, -1, 2 ** 40, -2 ** 40], np.int64)
+        assert m.murmur3_mix(ks.view(np.uint64)).tolist() == [
+            py_murmur3(int(k)) for k in ks]
+
+    def test_key_shapes(self):
+        m = self.mx()
+        for shape, fn in m.SHAPES.items():
+            assert fn.__doc__
+            for nb in m.SMALL_BUILDS + (8193,):
+                if nb < m.MIN_BUILD.get(shape, 0):
+                    continue
+                bk, bnull, pk, pnull = fn(nb, m.SMALL_M, seed=nb)
+                assert len(bk) == nb and len(pk) == m.SMALL_M
+                assert bk.dtype == np.int64 and pk.dtype == np.int64
+                assert bnull is None or len(bnull) == nb
+                assert pnull is None or len(pnull) == m.SMALL_M
+        bk, _, pk, _ = m.shape_unique(1000, 400)
+        assert len(set(bk.tolist())) == 1000
+        assert (np.abs(bk) > 2 ** 31).mean() > 0.99 and (bk < 0).any() and (bk > 0).any()
+        hits = np.isin(pk, bk)
+        assert hits[0::2].all() and not hits[1::2].any()
+        bk, _, pk, _ = m.shape_dups(1000, 400)
+        copies = np.unique(bk, return_counts=True)[1]
+        assert set(copies.tolist()) == {1, 2, 3, 4}
+        assert np.any(np.diff(bk) < 0)                       # shuffled
+        assert np.isin(pk, bk).mean() == 0.5
+        bk, _, pk, _ = m.shape_one_hot(1000, 400)
+        vals, copies = np.unique(bk, return_counts=True)
+        assert copies.max() == m.ONE_HOT_COPIES == 500 and (copies == 1).sum() == 500
+        assert (pk == vals[np.argmax(copies)]).sum() >= 100
+        bk, _, pk, _ = m.shape_all_miss(1000, 400)
+        assert not np.isin(pk, bk).any()
+        bk, _, pk, pnull = m.shape_all_null_probe(1000, 400)
+        assert pnull.all() and np.isin(pk, bk).all()         # would match if read
+        bk, bnull, pk, pnull = m.shape_nulls(1000, 400)
+        assert 0.01 < bnull.mean() < 0.06 and 0.01 < pnull.mean() < 0.06
+        assert np.isin(bk[bnull], pk).any()                  # would match if read
+        assert np.isin(pk[pnull], bk).any()
+        # a key held by a NULL build row only is asked for by a valid probe row
+        bk, bnull, pk, pnull = m.shape_nulls(1, 5)
+        assert bnull.all() and (pk[~pnull] == bk[0]).any()
+
+    @pytest.mark.parametrize("nb", [6, 63, 64, 65, 1000, 8193])
+    def test_colliding_shape(self, nb):
+        m = self.mx()
+        cap = m.join_hash_size(nb)
+        bk, _, pk, _ = m.shape_colliding(nb, m.SMALL_M)
+        bslot = m.slots_of(bk, cap)
+        a, d, b, e, c = (int(k) for k in pk[:5])
+        slot = int(m.slots_of(np.array([a]), cap)[0])
+        # the slot of A holds exactly the three distinct keys A, B and C
+        in_slot = bk[bslot == slot]
+        assert sorted(set(in_slot.tolist())) == sorted([a, b, c]) and len({a, b, c}) == 3
+        assert sorted(np.unique(in_slot, return_counts=True)[1].tolist()) == [1, 2, 3]
+        # D lands there and is absent; E lands in a slot no build key uses
+        assert int(m.slots_of(np.array([d]), cap)[0]) == slot and d not in bk
+        assert int(m.slots_of(np.array([e]), cap)[0]) not in set(bslot.tolist())
+        assert len(set(bk.tolist())) == nb - 3
+        # python restatement of the slot function agrees with numpy's
+        assert py_murmur3(a) & (cap - 1) == slot
+
+    def test_overflow_case_exceeds_first_cap(self):
+        m = self.mx()
+        bk, _, pk, _ = m.overflow_inputs()
+        n = m.OVERFLOW_N
+        assert len(bk) == len(pk) == n and len(set(bk.tolist()) | set(pk.tolist())) == 1
+        midx = len(pk)                        # non-NULL probe rows
+        src = open(m.os.path.join(m._CSRC, "ops_join.hip")).read()
+        assert "int64_t cap = midx + t.n + 64;" in src
+        assert n * n > midx + len(bk) + 64
+
+    def test_set_and_page_shapes(self):
+        m = self.mx()
+        s = m.set_shapes()
+        assert set(s) == set(m.SET_SHAPES)
+        rng_of = lambda k: int(k.max()) - int(k.min()) + 1
+        assert rng_of(s["range64"][0]) == 64 and rng_of(s["range65"][0]) == 65
+        assert rng_of(s["range128"][0]) == 128
+        assert s["runs_cross_words"][0].min() < 0
+        k = s["clustered"][0]
+        assert np.all(np.diff(k) >= 0)
+        # many lanes of a wave share a word: 64 sorted neighbours span few words
+        w = (k - k.min()) >> 6
+        assert max(len(set(w[i:i + 64].tolist())) for i in range(0, len(k), 64)) <= 3
+        assert len(s["n_not_multiple_of_64"][0]) % 64 and len(k) % 64
+        k, z = s["nulls_inside_run"]
+        assert z is not None and any(z[i] and k[i - 1] == k[i] == k[i + 1] and
+                                     not z[i - 1] and not z[i + 1]
+                                     for i in range(1, len(k) - 1))
+        k = s["runs_cross_words"][0]
+        w = (k - k.min()) >> 6
+        assert np.any((np.diff(w) == 1) & (np.diff(k) <= 1))   # a run crosses a word
+        assert max(m.WIDE_RANGE_KEYS) - min(m.WIDE_RANGE_KEYS) + 1 > 2 ** 33
+        # multi-page build: NULL rows only in pages that carry a bitmap, at odd
+        # bit offsets, first and last row of such a page included
+        assert m.MULTI_PAGE_SIZES == [37, 64, 0, 1, 100, 8000]
+        starts = np.cumsum([0] + m.MULTI_PAGE_SIZES)
+        assert any(st % 64 for st in starts[1:-1])
+        for shift in (1, 2):
+            for mask in m._multi_page_masks(shift):
+                assert mask.any()
+                for i, bm in enumerate(m.MULTI_PAGE_BITMAPS):
+                    if not bm:
+                        assert not mask[starts[i]:starts[i + 1]].any()
+        knull = m._multi_page_masks(1)[0]
+        assert knull[37] and knull[100] and knull[102] and knull[-1]
+        assert 0 < sum(m.MULTI_PAGE_BITMAPS) < len(m.MULTI_PAGE_BITMAPS)
+
+    def test_generic_tables_and_packing(self):
+        m = self.mx()
+        for name in m.GENERIC:
+            build, bk, probe, pk = m.generic_tables(name)
+            assert [c.kind for c in build] == [c.kind for c in probe]
+            bkeys, pkeys = m.keys_of(build, bk), m.keys_of(probe, pk)
+            ref = m.ref_join(bkeys, pkeys, True)
+            matched = [p for p in ref if p[1] is not None]
+            assert matched and len(matched) < len(ref)         # hits and misses
+            assert len(matched) > len({p for p, _ in matched})  # duplicates
+        build, bk, probe, pk = m.generic_tables("bigint_integer")
+        keys = m.keys_of(build, bk)
+        assert any(k[0] is None and k[1] is not None for k in keys)
+        assert any(k[1] is None and k[0] is not None for k in keys)
+        build, bk, probe, pk = m.generic_tables("varchar_bigint")
+        assert any(k[0] == b"" for k in m.keys_of(build, bk))   # '' is a value
+        assert any(k[0] is None for k in m.keys_of(build, bk))
+        build, bk, probe, pk = m.generic_tables("smallint_tinyint_date")
+        assert all(min(k[i] for k in m.keys_of(build, bk)) < 0 for i in range(3))
+        build, bk, probe, pk = m.generic_tables("double")
+        bits = set(build[0].values.view(np.uint64).tolist())
+        assert {0x7FF8000000000000, 0xFFF8000000000ABC, 0x8000000000000000, 0} <= bits
+        v = np.arange(130) % 3 != 0
+        w = m.pack_bits(v)
+        assert len(w) == 3 and int(w[0]) & 0b111 == 0b110
+        assert np.array_equal(m.unpack_bits(w, 130), v)
+        assert m.unpack_bits(None, 5).all()
+        for src_nulls in (False, True):
+            build, probe = m.outer_column_tables(src_nulls)
+            assert [c.kind for c in build] == ["i64", "i64", "f64", "i32", "date",
+                                               "i16", "i8", "str", "i64"]
+            assert all((c.valid is not None) == src_nulls for c in build[1:-1])

@@ -816,12 +816,14 @@ __global__ void k_gather_var_bytes(const uint8_t* __restrict__ src_bytes,
 
 static tg_status run_gather_var(tg_session* s, const DevBlock& src,
                                 const int32_t* d_positions, int32_t count,
-                                DevBlock* out)
+                                DevBlock* out, bool null_positions)
 {
     out->type = TG_VARCHAR;
     out->n = count;
     TG_POOL_ALLOC(s, &out->offsets, (int64_t)(count + 1) * 4);
-    if (src.valid) {
+    /* negative positions (probe-outer misses) become NULL even when the
+     * source column has no nulls of its own */
+    if (src.valid || null_positions) {
         int64_t words = (count + 63) / 64;
         TG_POOL_ALLOC(s, &out->valid, (words ? words : 1) * 8);
         TG_HIP_CHECK(hipMemsetAsync(out->valid, 0xFF, words * 8, s->stream));
@@ -854,7 +856,7 @@ tg_status run_gather(tg_session* s, const DevBlock& src, const int32_t* d_positi
                      int32_t count, DevBlock* out, bool null_positions)
 {
     if (src.type == TG_VARCHAR)
-        return run_gather_var(s, src, d_positions, count, out);
+        return run_gather_var(s, src, d_positions, count, out, null_positions);
     out->type = src.type;
     out->n = count;
     TG_POOL_ALLOC(s, &out->data, (int64_t)(count ? count : 1) * src.elem_size());

@@ -122,6 +122,15 @@ __device__ static inline bool probe_matches(const JoinTable& t, const ProbeKeys&
             for (int32_t k = 0; k < bl; k++)
                 if (bb[k] != pb[k]) return false;
         }
+        else if (bc.type == TG_DOUBLE) {
+            /* the join criterion `=` is IEEE ==: -0.0 matches 0.0 and NaN
+             * matches nothing (the canonical word is the GROUPING identity,
+             * where every NaN is one value; the hash stays canonical, so
+             * equal doubles still share a slot) */
+            if (!(((const double*)bc.data)[build_row] ==
+                  ((const double*)pc.data)[probe_row]))
+                return false;
+        }
         else if (kcol_word(bc, build_row) != kcol_word(pc, probe_row))
             return false;
     }
@@ -150,6 +159,36 @@ struct tg_join_bridge {
      * effort like the reference: generic keys / huge ranges skip it. */
     bool want_bitmap = false;
 };
+
+/* probe-side key channels must mirror the build's: same count and, per
+ * position, the same type. The probe kernels index the probe KColH array by
+ * the BUILD's channel count and pick the compare by the BUILD's type, so a
+ * mismatch would read past the array or through null VARCHAR offsets. */
+static tg_status check_probe_keys(const tg_join_bridge* b, const tg_page* page,
+                                  const int32_t* key_channels, size_t n_keys)
+{
+    if (n_keys != b->key_channels.size()) {
+        TG_SET_ERR("probe has %zu join key channels, the build has %zu",
+                   n_keys, b->key_channels.size());
+        return TG_ERR_INVALID_ARG;
+    }
+    for (size_t k = 0; k < n_keys; k++) {
+        int32_t ch = key_channels[k];
+        if (ch < 0 || ch >= page->channel_count) {
+            TG_SET_ERR("probe join key channel %d outside the page's %d channels",
+                       ch, page->channel_count);
+            return TG_ERR_INVALID_ARG;
+        }
+        int32_t bt = (int32_t)b->build_types[b->key_channels[k]];
+        int32_t pt = (int32_t)page->blocks[ch].type;
+        if (bt != pt) {
+            TG_SET_ERR("join key %zu type mismatch: probe channel %d has type %d, "
+                       "the build key has type %d", k, ch, pt, bt);
+            return TG_ERR_INVALID_ARG;
+        }
+    }
+    return TG_OK;
+}
 
 /* IncrementalLoadFactorHashArraySizeSupplier (multiplier 1) */
 static int64_t join_hash_size(int64_t expected)
@@ -528,7 +567,9 @@ __global__ void k_probe_count(JoinTable t, ProbeKeys p, int64_t m, int outer,
     for (; i < m; i += stride) {
         int32_t cnt = 0;
         int32_t head = -1;
-        if (!probe_null(t, p, i)) {
+        /* empty build: nothing matches and there is no table to walk (a
+         * generic-key probe has no pk for the legacy branch to read) */
+        if (t.n > 0 && !probe_null(t, p, i)) {
             int64_t slot = (int64_t)probe_slot(t, p, i);
             if (t.kv) {          /* one 16B read resolves most probes */
                 SlotKV e = t.kv[slot];
@@ -900,10 +941,8 @@ struct HashBuilderOp : tg_operator {
                 TG_HIP_CHECK(hipMemcpyAsync((char*)b.data + at * b.elem_size(),
                                             p.blocks[c].data, p.n * b.elem_size(),
                                             hipMemcpyDeviceToDevice, s->stream));
-                /* null bitmaps at arbitrary bit offsets: pages are
-                 * TG_BLOCK-row-aligned in practice; general repack via gather
-                 * kernel would go here — round 1 requires page sizes to be
-                 * multiples of 64 when nulls are present */
+                /* null bitmaps land at arbitrary bit offsets: k_bitmap_concat
+                 * clears bit (at + i) per null row, whatever the page sizes */
                 if (p.blocks[c].valid) {
                     hipLaunchKernelGGL(k_bitmap_concat, dim3(tg_grid_for(p.n)),
                                        dim3(TG_BLOCK), 0, s->stream, p.blocks[c].valid,
@@ -1080,6 +1119,10 @@ struct HashBuilderOp : tg_operator {
             tg_status mst = compute_key_range();
             if (mst != TG_OK) return mst;
         }
+        /* the legacy open-addressing build counts no indexed rows: take the
+         * semi join's "build has a NULL key" from the non-null key count */
+        if (!t.generic && !t.csr && !bitmap_built)
+            t.has_null_key = bridge->key_rows < total_rows ? 1 : 0;
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
         for (auto& p : pages) tg_free_page(s, &p);
         pages.clear();
@@ -1114,8 +1157,11 @@ struct LookupJoinOp : tg_operator {
     {
         if (!bridge->built) { TG_SET_ERR("lookup source not built (finish the builder first)"); return TG_ERR_STATE; }
         if (bridge->t.set_bitmap && !bridge->t.csr) { TG_SET_ERR("set-builder bridge supports semi join only"); return TG_ERR_UNSUPPORTED; }
+        tg_status st = check_probe_keys(bridge, page, key_channels.data(),
+                                        key_channels.size());
+        if (st != TG_OK) return st;
         DevPage in;
-        tg_status st = tg_upload_page(s, page, &in);
+        st = tg_upload_page(s, page, &in);
         if (st != TG_OK) return st;
         JoinTable& t = bridge->t;
         ProbeKeys pkc{};
@@ -1319,6 +1365,7 @@ extern "C" void tg_join_bridge_close(tg_join_bridge* b)
     for (auto& c : b->build_channels) {
         if (c.data) tg_pool_free(b->s, c.data);
         if (c.valid) tg_pool_free(b->s, c.valid);
+        if (c.offsets) tg_pool_free(b->s, c.offsets);
     }
     delete b;
 }
@@ -1361,6 +1408,7 @@ extern "C" tg_status tg_hash_builder_create(tg_session* s, tg_join_bridge* bridg
     for (int i = 0; i < n_build_channels; i++)
         op->types.push_back((tg_type)build_types[i]);
     bridge->build_types = op->types;
+    bridge->key_channels = op->key_channels;
     bridge->build_output_channels.assign(output_channels, output_channels + n_output_channels);
     *out = op;
     return TG_OK;
@@ -1377,10 +1425,13 @@ __global__ void k_semi_probe(JoinTable t, ProbeKeys p, int64_t m,
         /* three-valued IN semantics (HashSemiJoinOperator.java:180-201):
          * probe null -> false if the build set is empty, else NULL;
          * miss against a set containing NULL -> NULL. */
+        if (t.n == 0) {      /* empty build: false and valid, NULL probes too */
+            match[i] = 0;
+            continue;
+        }
         if (probe_null(t, p, i)) {
             match[i] = 0;
-            if (t.n > 0)
-                atomicAnd((unsigned long long*)&mvalid[i >> 6], ~(1ull << (i & 63)));
+            atomicAnd((unsigned long long*)&mvalid[i >> 6], ~(1ull << (i & 63)));
             continue;
         }
         int8_t hit = 0;
@@ -1434,8 +1485,17 @@ struct SemiJoinOp : tg_operator {
     tg_status add_input(const tg_page* page) override
     {
         if (!bridge->built) { TG_SET_ERR("lookup source not built"); return TG_ERR_STATE; }
+        /* the probe context below carries ONE key channel, while the kernels
+         * loop to the build's channel count */
+        if (bridge->key_channels.size() != 1) {
+            TG_SET_ERR("semi join takes a single key channel; the build has %zu",
+                       bridge->key_channels.size());
+            return TG_ERR_UNSUPPORTED;
+        }
+        tg_status st = check_probe_keys(bridge, page, &key_channel, 1);
+        if (st != TG_OK) return st;
         DevPage in;
-        tg_status st = tg_upload_page(s, page, &in);
+        st = tg_upload_page(s, page, &in);
         if (st != TG_OK) return st;
         JoinTable& jt = bridge->t;
         ProbeKeys pkc{};

@@ -457,9 +457,11 @@ def semi_join(session, bridge, key_channel):
     return Operator(session, h)
 
 
-def page_with_varchar(columns):
+def page_with_varchar(columns, valids=None):
     """Build a page where entries may be numpy arrays (fixed width) or
-    (bytes_array_uint8, offsets_int32) tuples for VARCHAR channels."""
+    (bytes_array_uint8, offsets_int32) tuples for VARCHAR channels.
+    valids: optional list of packed uint64 bitmaps (bit=1 valid) or None per
+    column, as in page_from_numpy."""
     n = None
     for c in columns:
         n = len(c[1]) - 1 if isinstance(c, tuple) else len(c)
@@ -483,6 +485,9 @@ def page_with_varchar(columns):
             blocks[i].on_device = 0
             blocks[i].data = col.ctypes.data
             keep.append(col)
+        v = valids[i] if valids else None
+        blocks[i].valid = v.ctypes.data if v is not None else None
+        keep.append(v)
     p = TgPage()
     p.channel_count = len(columns)
     p.position_count = blocks[0].position_count
