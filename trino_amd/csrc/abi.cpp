@@ -117,6 +117,7 @@ extern "C" void tg_session_close(tg_session* s)
 {
     if (!s) return;
     if (s->pin_buf) (void)hipHostFree(s->pin_buf);
+    tg_q1_scratch_free(s);
     for (auto& kv : s->pool_sizes) (void)hipFree(kv.first);
     (void)hipEventDestroy(s->ev_start);
     (void)hipEventDestroy(s->ev_stop);

@@ -39,7 +39,15 @@ struct tg_session {
     size_t mem_cap = 0;                       /* soft cap (92% of VRAM) */
     void* pin_buf = nullptr;                  /* pinned DtoH staging buffer */
     size_t pin_cap = 0;
+    /* Q1 working set (q1.hip: q1_ensure_scratch / tg_q1_scratch_free) */
+    unsigned long long* q1_partials = nullptr;   /* [60 words][TG_MAX_BLOCKS] */
+    unsigned long long* q1_result = nullptr;     /* 60 words, pinned + mapped */
+    unsigned long long* q1_result_dev = nullptr; /* device view of q1_result */
+    double* q1_naive_sums = nullptr;
+    long long* q1_naive_cnts = nullptr;
 };
+
+void tg_q1_scratch_free(tg_session* s);
 
 tg_status tg_pool_alloc(tg_session* s, void** out, size_t bytes);
 void tg_pool_free(tg_session* s, void* p);

@@ -18,6 +18,25 @@
  * The final sums are the correctly-rounded exact sums, order-independent —
  * bit-equal to oracle o_q1_exact. sum(quantity) and count are exact integers.
  *
+ * Structure of a step (two launches, no copy):
+ *   k_q1_fused  one pass over the columns, 4 rows per lane per iteration.
+ *     - The row loop is software-pipelined: the eleven loads (seven columns) of group
+ *       i + stride are issued into a second register set before the ALU work
+ *       on group i, so every wave keeps 152 B/lane in flight while it
+ *       computes.
+ *     - Per-lane sums are 96-bit and counts 32-bit (bounded by rows per
+ *       lane, checked on the host) and widened at the wave reduce.
+ *     - The six combo sections are guarded by one per-lane "combos present"
+ *       bitmask, one wave vote per section.
+ *     - Block partials go out word-major: partials[word][block].
+ *   k_q1_merge  36 blocks, one per (combo, field); each reads its word's
+ *     partials with unit stride, adds them as u128 and writes the final
+ *     words straight into the session's pinned, device-mapped result block.
+ *
+ * Measured at SF100 on MI355X (profiles/q1_pipelined_vs_parent.txt): step
+ * 4.19 -> 3.81 ms; scan 3.8 ms = 6.0 TB/s of the ~6.3 TB/s a streaming read
+ * reaches; merge 4.6 us where the serial reduce + result copy took 0.14 ms.
+ *
  * Parity-mode kernel (k_q1_naive_seq): single thread, reference sequential
  * order — bit-equal to oracle o_q1_naive for page-sized operator tests.
  */
@@ -27,16 +46,126 @@
 #define NCOMBO 6
 #define S43 8796093022208.0        /* 2^43 */
 #define S59 576460752303423488.0   /* 2^59 */
+#define Q1_R 4                     /* rows per lane per iteration */
 
-/* per-block partial layout: per combo 10 u64 words:
- * base(2) dp(2) ch(2) disc(2) qty(1) cnt(1) => 60 words per block */
+/* result layout: per combo 10 u64 words:
+ * base(2) dp(2) ch(2) disc(2) qty(1) cnt(1) => 60 words.
+ * partials are word-major: word w of block b is partials[w * TG_MAX_BLOCKS + b] */
 #define PARTIAL_WORDS (NCOMBO * 10)
 
-struct lane_acc {
-    u128 base, dp, ch, disc;
-    unsigned long long qty;
-    unsigned long long cnt;
+typedef double q1_f64x2 __attribute__((ext_vector_type(2)));
+typedef int q1_i32x4 __attribute__((ext_vector_type(4)));
+
+/* trunc(x * scale) as u64 for x >= 0, x * scale < 2^63 (scale a power of
+ * two, so the product is exact) — the oracle's (long long)(x * S). An
+ * integer-only version taken from the mantissa (seven 32-bit instructions
+ * instead of seven f64 ones) was measured and showed no gain once the loop is
+ * pipelined — the scan is HBM-bound — so the plain cast stays
+ * (profiles/q1_pipelined_vs_parent.txt). */
+__device__ static inline unsigned long long fx_trunc(double x, double scale)
+{
+    return (unsigned long long)(x * scale);
+}
+
+/* one lane's four rows of the seven columns (38 VGPRs) */
+struct q1_rows {
+    q1_f64x2 q[2], e[2], d[2], t[2];
+    q1_i32x4 sd;
+    unsigned rf, ls;   /* 4 packed bytes each */
 };
+
+/* the columns are read once and are 90x the Infinity Cache: nontemporal
+ * loads (measured 4.14 -> 3.81 ms per SF100 step against plain loads) */
+__device__ static inline void q1_load(q1_rows& g, int64_t r,
+                                      const int32_t* __restrict__ shipdate,
+                                      const double* __restrict__ qty,
+                                      const double* __restrict__ extprice,
+                                      const double* __restrict__ disc,
+                                      const double* __restrict__ tax,
+                                      const uint8_t* __restrict__ rflag,
+                                      const uint8_t* __restrict__ lstatus)
+{
+    const q1_f64x2* pq = reinterpret_cast<const q1_f64x2*>(qty + r);
+    const q1_f64x2* pe = reinterpret_cast<const q1_f64x2*>(extprice + r);
+    const q1_f64x2* pd = reinterpret_cast<const q1_f64x2*>(disc + r);
+    const q1_f64x2* pt = reinterpret_cast<const q1_f64x2*>(tax + r);
+    g.q[0] = __builtin_nontemporal_load(pq); g.q[1] = __builtin_nontemporal_load(pq + 1);
+    g.e[0] = __builtin_nontemporal_load(pe); g.e[1] = __builtin_nontemporal_load(pe + 1);
+    g.d[0] = __builtin_nontemporal_load(pd); g.d[1] = __builtin_nontemporal_load(pd + 1);
+    g.t[0] = __builtin_nontemporal_load(pt); g.t[1] = __builtin_nontemporal_load(pt + 1);
+    g.sd = __builtin_nontemporal_load(reinterpret_cast<const q1_i32x4*>(shipdate + r));
+    g.rf = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(rflag + r));
+    g.ls = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(lstatus + r));
+}
+
+/* per-lane accumulators of one combo: the four u128 sums are kept as 96 bits
+ * (a lane adds at most one carry per row into the top word, and the host
+ * bounds rows per lane below 2^32), the count as 32 — 15 VGPRs per combo */
+struct acc96 { unsigned w0, w1, w2; };
+struct lane_acc {
+    acc96 base, dp, ch, disc;
+    unsigned long long qty;
+    unsigned cnt;
+};
+
+/* three-instruction carry chain, in place */
+__device__ static inline void acc_add(acc96& a, unsigned long long y)
+{
+    unsigned c0, c1;
+    a.w0 = __builtin_addc(a.w0, (unsigned)y, 0u, &c0);
+    a.w1 = __builtin_addc(a.w1, (unsigned)(y >> 32), c0, &c1);
+    a.w2 += c1;
+}
+
+/* add one row's values to combo c; c must be a compile-time constant at
+ * every call: a runtime acc[c] index demotes the
+ * whole accumulator array to scratch (measured: 496 B/lane, 18% roofline) */
+#define Q1_ACC_ADD(c, tb, tp, tc, td, tq, tn) do { \
+    acc_add(acc[c].base, (tb)); \
+    acc_add(acc[c].dp, (tp)); \
+    acc_add(acc[c].ch, (tc)); \
+    acc_add(acc[c].disc, (td)); \
+    acc[c].qty += (tq); \
+    acc[c].cnt += (tn); } while (0)
+
+__device__ static inline void q1_accumulate(lane_acc (&acc)[NCOMBO], const q1_rows& g,
+                                            int32_t cutoff)
+{
+    const double vq[Q1_R] = { g.q[0].x, g.q[0].y, g.q[1].x, g.q[1].y };
+    const double ve[Q1_R] = { g.e[0].x, g.e[0].y, g.e[1].x, g.e[1].y };
+    const double vd[Q1_R] = { g.d[0].x, g.d[0].y, g.d[1].x, g.d[1].y };
+    const double vt[Q1_R] = { g.t[0].x, g.t[0].y, g.t[1].x, g.t[1].y };
+    const int32_t sd[Q1_R] = { g.sd.x, g.sd.y, g.sd.z, g.sd.w };
+    unsigned sc[Q1_R];      /* combo of a selected row, 0xffff otherwise */
+    unsigned present = 0;   /* bit c: this lane has a selected row of combo c */
+    unsigned long long yb[Q1_R], yp[Q1_R], yc[Q1_R], yd[Q1_R], yq[Q1_R];
+    #pragma unroll
+    for (int j = 0; j < Q1_R; j++) {
+        const unsigned cb = ((g.rf >> (8 * j)) & 0xffu) * 2 + ((g.ls >> (8 * j)) & 0xffu);
+        const bool sel = sd[j] <= cutoff;
+        sc[j] = sel ? cb : 0xffffu;
+        present |= sel ? (1u << (cb & 31u)) : 0u;
+        const double dp = ve[j] * (1.0 - vd[j]);
+        const double ch = dp * (1.0 + vt[j]);
+        yb[j] = fx_trunc(ve[j], S43);
+        yp[j] = fx_trunc(dp, S43);
+        yc[j] = fx_trunc(ch, S43);
+        yd[j] = fx_trunc(vd[j], S59);
+        yq[j] = fx_trunc(vq[j], 1.0);
+    }
+    #pragma unroll
+    for (int c = 0; c < NCOMBO; c++) {
+        if (__any((int)(present & (1u << c)))) {
+            /* rows are added in place under the lane mask: no selects, no
+             * temporaries; every add is a three-word carry chain */
+            #pragma unroll
+            for (int j = 0; j < Q1_R; j++) {
+                if (sc[j] == (unsigned)c)
+                    Q1_ACC_ADD(c, yb[j], yp[j], yc[j], yd[j], yq[j], 1u);
+            }
+        }
+    }
+}
 
 __device__ static inline void wave_reduce_u128(u128& v)
 {
@@ -57,8 +186,7 @@ __device__ static inline void wave_reduce_u64(unsigned long long& v)
         v += __shfl_xor(v, off, 64);
 }
 
-template <int R>   /* rows per lane per iteration (2 or 4) */
-__global__ __launch_bounds__(TG_BLOCK, R == 2 ? 3 : 2)   /* 2nd arg: waves/SIMD */
+__global__ __launch_bounds__(TG_BLOCK, 2)   /* 2nd arg: waves/SIMD */
 void k_q1_fused(int64_t n, const int32_t* __restrict__ shipdate,
                 const double* __restrict__ qty, const double* __restrict__ extprice,
                 const double* __restrict__ disc, const double* __restrict__ tax,
@@ -67,99 +195,48 @@ void k_q1_fused(int64_t n, const int32_t* __restrict__ shipdate,
 {
     lane_acc acc[NCOMBO];
     #pragma unroll
-    for (int c = 0; c < NCOMBO; c++) { acc[c].qty = 0; acc[c].cnt = 0; }
+    for (int c = 0; c < NCOMBO; c++) {
+        acc[c].base = acc[c].dp = acc[c].ch = acc[c].disc = acc96{0u, 0u, 0u};
+        acc[c].qty = 0;
+        acc[c].cnt = 0;
+    }
 
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;   /* lanes total */
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t ngrp = n / R;
+    const int64_t ngrp = n / Q1_R;
 
-    for (int64_t i = gid; i < ngrp; i += stride) {
-        const int64_t r = R * i;
-        double vq[R], ve[R], vd[R], vt[R];
-        int32_t sd[R];
-        uint8_t rf[R], ls[R];
-        #pragma unroll
-        for (int j = 0; j < R; j += 2) {   /* 16 B/lane vector loads */
-            *reinterpret_cast<double2*>(vq + j) = *reinterpret_cast<const double2*>(qty + r + j);
-            *reinterpret_cast<double2*>(ve + j) = *reinterpret_cast<const double2*>(extprice + r + j);
-            *reinterpret_cast<double2*>(vd + j) = *reinterpret_cast<const double2*>(disc + r + j);
-            *reinterpret_cast<double2*>(vt + j) = *reinterpret_cast<const double2*>(tax + r + j);
-        }
-        if (R == 4) {
-            *reinterpret_cast<int4*>(sd) = *reinterpret_cast<const int4*>(shipdate + r);
-            *reinterpret_cast<uchar4*>(rf) = *reinterpret_cast<const uchar4*>(rflag + r);
-            *reinterpret_cast<uchar4*>(ls) = *reinterpret_cast<const uchar4*>(lstatus + r);
-        }
-        else {
-            *reinterpret_cast<int2*>(sd) = *reinterpret_cast<const int2*>(shipdate + r);
-            *reinterpret_cast<uchar2*>(rf) = *reinterpret_cast<const uchar2*>(rflag + r);
-            *reinterpret_cast<uchar2*>(ls) = *reinterpret_cast<const uchar2*>(lstatus + r);
-        }
-        bool sel[R];
-        int cb[R];
-        unsigned long long yb[R], yp[R], yc[R], yd[R], yq[R];
-        #pragma unroll
-        for (int j = 0; j < R; j++) {
-            sel[j] = sd[j] <= cutoff;
-            cb[j] = rf[j] * 2 + ls[j];
-            double dp = ve[j] * (1.0 - vd[j]);
-            double ch = dp * (1.0 + vt[j]);
-            yb[j] = (unsigned long long)(ve[j] * S43);
-            yp[j] = (unsigned long long)(dp * S43);
-            yc[j] = (unsigned long long)(ch * S43);
-            yd[j] = (unsigned long long)(vd[j] * S59);
-            yq[j] = (unsigned long long)vq[j];
-        }
-        #pragma unroll
-        for (int c = 0; c < NCOMBO; c++) {
-            bool any = false;
-            #pragma unroll
-            for (int j = 0; j < R; j++) any |= (sel[j] & (cb[j] == c));
-            if (__any(any)) {
-                /* combine R masked rows into ONE u64 per sum (< 2^63), then a
-                 * single u128 add per sum per combo */
-                unsigned long long tb = 0, tp = 0, tc = 0, td = 0, tq = 0;
-                int tn = 0;
-                #pragma unroll
-                for (int j = 0; j < R; j++) {
-                    unsigned long long k = (sel[j] & (cb[j] == c)) ? ~0ull : 0ull;
-                    tb += yb[j] & k; tp += yp[j] & k; tc += yc[j] & k;
-                    td += yd[j] & k; tq += yq[j] & k;
-                    tn += (int)(k & 1);
-                }
-                acc[c].base.add(tb);
-                acc[c].dp.add(tp);
-                acc[c].ch.add(tc);
-                acc[c].disc.add(td);
-                acc[c].qty += tq;
-                acc[c].cnt += tn;
-            }
-        }
+    /* software pipeline: `cur` holds group i, `nxt` receives group i + stride
+     * while `cur` is computed on. The prefetch is unconditional in control
+     * flow — a skipped load block would force every later wait to drain the
+     * whole queue — so a lane's last iteration re-reads its own group i
+     * (in bounds, discarded). No lane reads past row ngrp * 4 <= n. */
+    if (gid < ngrp) {
+        int64_t i = gid;
+        q1_rows cur, nxt;
+        q1_load(cur, Q1_R * i, shipdate, qty, extprice, disc, tax, rflag, lstatus);
+        do {
+            const int64_t in = i + stride;
+            const int64_t ip = in < ngrp ? in : i;
+            q1_load(nxt, Q1_R * ip, shipdate, qty, extprice, disc, tax, rflag, lstatus);
+            q1_accumulate(acc, cur, cutoff);
+            cur = nxt;
+            i = in;
+        } while (i < ngrp);
     }
-    /* leftover rows [ngrp*R, n) handled by the first lane. NOTE: combo index
-     * must be compile-time constant per unrolled iteration — a runtime acc[c]
-     * index demotes the whole accumulator array to scratch (measured:
-     * 496 B/lane, 18% roofline). */
-    for (int64_t r = ngrp * R; gid == 0 && r < n; r++) {
+    /* leftover rows [ngrp*4, n) handled by the first lane */
+    for (int64_t r = ngrp * Q1_R; gid == 0 && r < n; r++) {
         if (shipdate[r] <= cutoff) {
             int ct = rflag[r] * 2 + lstatus[r];
             double dpv = extprice[r] * (1.0 - disc[r]);
             double chv = dpv * (1.0 + tax[r]);
-            unsigned long long tb = (unsigned long long)(extprice[r] * S43);
-            unsigned long long tp = (unsigned long long)(dpv * S43);
-            unsigned long long tc = (unsigned long long)(chv * S43);
-            unsigned long long td = (unsigned long long)(disc[r] * S59);
-            unsigned long long tq = (unsigned long long)qty[r];
+            unsigned long long tb = fx_trunc(extprice[r], S43);
+            unsigned long long tp = fx_trunc(dpv, S43);
+            unsigned long long tc = fx_trunc(chv, S43);
+            unsigned long long td = fx_trunc(disc[r], S59);
+            unsigned long long tq = fx_trunc(qty[r], 1.0);
             #pragma unroll
             for (int c = 0; c < NCOMBO; c++) {
-                if (ct == c) {
-                    acc[c].base.add(tb);
-                    acc[c].dp.add(tp);
-                    acc[c].ch.add(tc);
-                    acc[c].disc.add(td);
-                    acc[c].qty += tq;
-                    acc[c].cnt += 1;
-                }
+                if (ct == c) Q1_ACC_ADD(c, tb, tp, tc, td, tq, 1u);
             }
         }
     }
@@ -170,96 +247,93 @@ void k_q1_fused(int64_t n, const int32_t* __restrict__ shipdate,
     const int lane = threadIdx.x % 64;
     #pragma unroll
     for (int c = 0; c < NCOMBO; c++) {
-        wave_reduce_u128(acc[c].base);
-        wave_reduce_u128(acc[c].dp);
-        wave_reduce_u128(acc[c].ch);
-        wave_reduce_u128(acc[c].disc);
-        wave_reduce_u64(acc[c].qty);
-        wave_reduce_u64(acc[c].cnt);
+        u128 b, p, h, d;
+        #define Q1_WIDEN(v, a) do { v.lo = ((unsigned long long)(a).w1 << 32) | (a).w0; v.hi = (a).w2; } while (0)
+        Q1_WIDEN(b, acc[c].base);
+        Q1_WIDEN(p, acc[c].dp);
+        Q1_WIDEN(h, acc[c].ch);
+        Q1_WIDEN(d, acc[c].disc);
+        #undef Q1_WIDEN
+        unsigned long long q = acc[c].qty, k = acc[c].cnt;
+        wave_reduce_u128(b);
+        wave_reduce_u128(p);
+        wave_reduce_u128(h);
+        wave_reduce_u128(d);
+        wave_reduce_u64(q);
+        wave_reduce_u64(k);
         if (lane == 0) {
             unsigned long long* w = lds[wave] + c * 10;
-            w[0] = acc[c].base.lo; w[1] = acc[c].base.hi;
-            w[2] = acc[c].dp.lo;   w[3] = acc[c].dp.hi;
-            w[4] = acc[c].ch.lo;   w[5] = acc[c].ch.hi;
-            w[6] = acc[c].disc.lo; w[7] = acc[c].disc.hi;
-            w[8] = acc[c].qty;     w[9] = acc[c].cnt;
+            w[0] = b.lo; w[1] = b.hi;
+            w[2] = p.lo; w[3] = p.hi;
+            w[4] = h.lo; w[5] = h.hi;
+            w[6] = d.lo; w[7] = d.hi;
+            w[8] = q;    w[9] = k;
         }
     }
     __syncthreads();
     if (threadIdx.x < PARTIAL_WORDS) {
         const int f = threadIdx.x;          /* one word per thread */
         const int is_hi = ((f % 10) < 8) && (f % 2 == 1);
-        unsigned long long lo = 0, carryhi = 0;
+        unsigned long long* pw = partials + (int64_t)f * TG_MAX_BLOCKS + blockIdx.x;
         if (!is_hi && (f % 10) < 8) {
-            /* lo word of a u128 field: sum los with carry into hi below */
-            unsigned long long hs = 0;
+            /* lo word of a u128 field: sum los, carries go into the hi word */
+            unsigned long long lo = 0, hisum = 0;
             #pragma unroll
             for (int w = 0; w < TG_BLOCK / 64; w++) {
                 unsigned long long x = lds[w][f];
                 lo += x;
-                hs += (lo < x);
-                carryhi = hs;
+                hisum += (lo < x);
             }
-            unsigned long long hisum = carryhi;
             #pragma unroll
             for (int w = 0; w < TG_BLOCK / 64; w++) hisum += lds[w][f + 1];
-            partials[(int64_t)blockIdx.x * PARTIAL_WORDS + f] = lo;
-            partials[(int64_t)blockIdx.x * PARTIAL_WORDS + f + 1] = hisum;
+            pw[0] = lo;
+            pw[TG_MAX_BLOCKS] = hisum;
         }
         else if ((f % 10) >= 8) {
             unsigned long long s = 0;
             #pragma unroll
             for (int w = 0; w < TG_BLOCK / 64; w++) s += lds[w][f];
-            partials[(int64_t)blockIdx.x * PARTIAL_WORDS + f] = s;
+            pw[0] = s;
         }
         /* hi words written by their lo-word thread */
     }
 }
 
-/* final cross-block reduce: 36 (combo,field) owners × 7 block-chunks */
-#define RED_CHUNKS 7
-__global__ void k_q1_reduce(const unsigned long long* __restrict__ partials,
-                            int nblocks, unsigned long long* __restrict__ out)
+/* final cross-block merge: block (c, f) owns field f of combo c (f < 4: a
+ * u128 sum, f = 4 qty, f = 5 count) and reads that word's partials with unit
+ * stride across blocks. `out` is the session's device-mapped pinned block. */
+#define MERGE_FIELDS 6
+__global__ __launch_bounds__(TG_BLOCK)
+void k_q1_merge(const unsigned long long* __restrict__ partials, int nblocks,
+                unsigned long long* __restrict__ out)
 {
-    __shared__ unsigned long long plo[NCOMBO * 6][RED_CHUNKS];
-    __shared__ unsigned long long phi[NCOMBO * 6][RED_CHUNKS];
-    int t = threadIdx.x;
-    int fld = t % (NCOMBO * 6);
-    int chunk = t / (NCOMBO * 6);
-    if (chunk < RED_CHUNKS) {
-        int c = fld / 6, f = fld % 6;
-        int per = (nblocks + RED_CHUNKS - 1) / RED_CHUNKS;
-        int b0 = chunk * per, b1 = min(b0 + per, nblocks);
-        u128 s;
-        if (f < 4) {
-            for (int b = b0; b < b1; b++) {
-                const unsigned long long* p = partials + (int64_t)b * PARTIAL_WORDS + c * 10 + f * 2;
-                u128 v; v.lo = p[0]; v.hi = p[1];
-                s.add128(v);
-            }
-        }
-        else {
-            for (int b = b0; b < b1; b++)
-                s.lo += partials[(int64_t)b * PARTIAL_WORDS + c * 10 + 8 + (f - 4)];
-        }
-        plo[fld][chunk] = s.lo;
-        phi[fld][chunk] = s.hi;
+    const int c = blockIdx.x / MERGE_FIELDS, f = blockIdx.x % MERGE_FIELDS;
+    const int word = c * 10 + (f < 4 ? 2 * f : 8 + (f - 4));
+    const unsigned long long* plo = partials + (int64_t)word * TG_MAX_BLOCKS;
+    const unsigned long long* phi = plo + TG_MAX_BLOCKS;
+    u128 s;
+    for (int b = threadIdx.x; b < nblocks; b += TG_BLOCK) {
+        u128 v;
+        v.lo = plo[b];
+        v.hi = f < 4 ? phi[b] : 0ull;
+        s.add128(v);
+    }
+    wave_reduce_u128(s);
+    __shared__ unsigned long long wl[TG_BLOCK / 64], wh[TG_BLOCK / 64];
+    if (threadIdx.x % 64 == 0) {
+        wl[threadIdx.x / 64] = s.lo;
+        wh[threadIdx.x / 64] = s.hi;
     }
     __syncthreads();
-    if (t < NCOMBO * 6) {
-        int c = t / 6, f = t % 6;
-        u128 s;
-        for (int k = 0; k < RED_CHUNKS; k++) {
-            u128 v; v.lo = plo[t][k]; v.hi = phi[t][k];
-            s.add128(v);
+    if (threadIdx.x == 0) {
+        u128 t;
+        #pragma unroll
+        for (int w = 0; w < TG_BLOCK / 64; w++) {
+            u128 v; v.lo = wl[w]; v.hi = wh[w];
+            t.add128(v);
         }
-        if (f < 4) {
-            out[c * 10 + f * 2] = s.lo;
-            out[c * 10 + f * 2 + 1] = s.hi;
-        }
-        else {
-            out[c * 10 + 8 + (f - 4)] = s.lo;
-        }
+        out[word] = t.lo;
+        if (f < 4) out[word + 1] = t.hi;
     }
 }
 
@@ -291,63 +365,69 @@ __global__ void k_q1_naive_seq(int64_t n, const int32_t* shipdate, const double*
     }
 }
 
-struct q1_scratch {
-    unsigned long long* partials = nullptr;
-    unsigned long long* out = nullptr;
-    double* naive_sums = nullptr;
-    long long* naive_cnts = nullptr;
-};
-static q1_scratch g_scratch;   /* per-process; one session per process */
-
-static tg_status ensure_scratch()
+/* the session owns Q1's working set; tg_session_close frees it */
+static tg_status q1_ensure_scratch(tg_session* s)
 {
-    if (!g_scratch.partials) {
-        TG_HIP_CHECK(hipMalloc(&g_scratch.partials,
-                               (size_t)TG_MAX_BLOCKS * PARTIAL_WORDS * 8));
-        TG_HIP_CHECK(hipMalloc(&g_scratch.out, PARTIAL_WORDS * 8));
-        TG_HIP_CHECK(hipMalloc(&g_scratch.naive_sums, NCOMBO * 5 * 8));
-        TG_HIP_CHECK(hipMalloc(&g_scratch.naive_cnts, NCOMBO * 8));
+    if (!s->q1_partials)
+        TG_HIP_CHECK(hipMalloc(&s->q1_partials, (size_t)TG_MAX_BLOCKS * PARTIAL_WORDS * 8));
+    if (!s->q1_result_dev) {
+        if (!s->q1_result)
+            TG_HIP_CHECK(hipHostMalloc((void**)&s->q1_result, PARTIAL_WORDS * 8, hipHostMallocMapped));
+        TG_HIP_CHECK(hipHostGetDevicePointer((void**)&s->q1_result_dev, s->q1_result, 0));
     }
+    if (!s->q1_naive_sums)
+        TG_HIP_CHECK(hipMalloc(&s->q1_naive_sums, NCOMBO * 5 * 8));
+    if (!s->q1_naive_cnts)
+        TG_HIP_CHECK(hipMalloc(&s->q1_naive_cnts, NCOMBO * 8));
     return TG_OK;
+}
+
+void tg_q1_scratch_free(tg_session* s)
+{
+    if (s->q1_partials) (void)hipFree(s->q1_partials);
+    if (s->q1_result) (void)hipHostFree(s->q1_result);
+    if (s->q1_naive_sums) (void)hipFree(s->q1_naive_sums);
+    if (s->q1_naive_cnts) (void)hipFree(s->q1_naive_cnts);
+    s->q1_partials = s->q1_result = s->q1_result_dev = nullptr;
+    s->q1_naive_sums = nullptr;
+    s->q1_naive_cnts = nullptr;
 }
 
 extern "C" tg_status tg_q1_run(tg_session* s, const tg_tpch_lineitem_cols* cols,
                                int32_t cutoff, tg_q1_result* out)
 {
     if (!s || !cols || !out) { TG_SET_ERR("null arg"); return TG_ERR_INVALID_ARG; }
-    tg_status st = ensure_scratch();
+    tg_status st = q1_ensure_scratch(s);
     if (st != TG_OK) return st;
     int64_t n = cols->row_count;
-    /* variant/grid sweep hooks (defaults measured on MI355X: R=4, 1536
-     * blocks -> 6.0 TB/s = 75% of the 8 TB/s roofline; profiles/r01) */
-    static int R = [] { const char* e = getenv("TG_Q1_R"); return e ? atoi(e) : 4; }();
+    /* grid sweep hook (default measured on MI355X; profiles/q1_pipelined_vs_parent.txt) */
     static int blocks_env = [] { const char* e = getenv("TG_Q1_BLOCKS"); return e ? atoi(e) : 0; }();
-    int grid = tg_grid_for(n, R);
+    int grid = tg_grid_for(n, Q1_R);
     if (grid > 1536) grid = 1536;
     if (blocks_env > 0) grid = blocks_env;
     if (grid > TG_MAX_BLOCKS) grid = TG_MAX_BLOCKS;   /* partials buffer bound */
+    /* the per-lane carry words and counts are 32-bit */
+    if (n / ((int64_t)grid * TG_BLOCK) >= 0xfffffff0ll) {
+        TG_SET_ERR("q1: %lld rows exceed the per-lane 32-bit row bound", (long long)n);
+        return TG_ERR_INVALID_ARG;
+    }
     TG_HIP_CHECK(hipEventRecord(s->ev_start, s->stream));
-    if (R == 4)
-        hipLaunchKernelGGL(k_q1_fused<4>, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                           n, cols->shipdate, cols->quantity, cols->extendedprice,
-                           cols->discount, cols->tax, cols->returnflag, cols->linestatus,
-                           cutoff, g_scratch.partials);
-    else
-        hipLaunchKernelGGL(k_q1_fused<2>, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                           n, cols->shipdate, cols->quantity, cols->extendedprice,
-                           cols->discount, cols->tax, cols->returnflag, cols->linestatus,
-                           cutoff, g_scratch.partials);
+    hipLaunchKernelGGL(k_q1_fused, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
+                       n, cols->shipdate, cols->quantity, cols->extendedprice,
+                       cols->discount, cols->tax, cols->returnflag, cols->linestatus,
+                       cutoff, s->q1_partials);
     TG_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_q1_merge, dim3(NCOMBO * MERGE_FIELDS), dim3(TG_BLOCK), 0, s->stream,
+                       s->q1_partials, grid, s->q1_result_dev);
+    TG_HIP_CHECK(hipGetLastError());
+    /* the events bracket the scan and its merge */
     TG_HIP_CHECK(hipEventRecord(s->ev_stop, s->stream));
-    hipLaunchKernelGGL(k_q1_reduce, dim3(1), dim3(256), 0, s->stream,
-                       g_scratch.partials, grid, g_scratch.out);
-    TG_HIP_CHECK(hipGetLastError());
-    unsigned long long h[PARTIAL_WORDS];
-    TG_HIP_CHECK(hipMemcpyAsync(h, g_scratch.out, sizeof(h), hipMemcpyDeviceToHost, s->stream));
     TG_HIP_CHECK(hipStreamSynchronize(s->stream));
     float ms = 0;
     TG_HIP_CHECK(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
 
+    unsigned long long h[PARTIAL_WORDS];
+    memcpy(h, s->q1_result, sizeof(h));
     memset(out, 0, sizeof(*out));
     memcpy(out->raw, h, sizeof(h));
     for (int c = 0; c < NCOMBO; c++) {
@@ -377,18 +457,18 @@ extern "C" tg_status tg_q1_run_naive(tg_session* s, const tg_tpch_lineitem_cols*
                                      int32_t cutoff, tg_q1_result* out)
 {
     if (!s || !cols || !out) { TG_SET_ERR("null arg"); return TG_ERR_INVALID_ARG; }
-    tg_status st = ensure_scratch();
+    tg_status st = q1_ensure_scratch(s);
     if (st != TG_OK) return st;
     hipLaunchKernelGGL(k_q1_naive_seq, dim3(1), dim3(64), 0, s->stream,
                        cols->row_count, cols->shipdate, cols->quantity,
                        cols->extendedprice, cols->discount, cols->tax,
                        cols->returnflag, cols->linestatus, cutoff,
-                       g_scratch.naive_sums, g_scratch.naive_cnts);
+                       s->q1_naive_sums, s->q1_naive_cnts);
     TG_HIP_CHECK(hipGetLastError());
     double hs[NCOMBO * 5];
     long long hc[NCOMBO];
-    TG_HIP_CHECK(hipMemcpyAsync(hs, g_scratch.naive_sums, sizeof(hs), hipMemcpyDeviceToHost, s->stream));
-    TG_HIP_CHECK(hipMemcpyAsync(hc, g_scratch.naive_cnts, sizeof(hc), hipMemcpyDeviceToHost, s->stream));
+    TG_HIP_CHECK(hipMemcpyAsync(hs, s->q1_naive_sums, sizeof(hs), hipMemcpyDeviceToHost, s->stream));
+    TG_HIP_CHECK(hipMemcpyAsync(hc, s->q1_naive_cnts, sizeof(hc), hipMemcpyDeviceToHost, s->stream));
     TG_HIP_CHECK(hipStreamSynchronize(s->stream));
     memset(out, 0, sizeof(*out));
     for (int c = 0; c < NCOMBO; c++) {
