@@ -93,7 +93,20 @@ tg_status tg_session_create(int device_ordinal, tg_session** out);
 void      tg_session_close(tg_session*);
 
 /* ---- expression IR (replaces per-query bytecode gen, sql/gen/columnar/) ----
- * Postfix program over f64/i64 lanes; enough for TPC-H filter/project forms. */
+ * Postfix program over f64/i64 lanes; enough for TPC-H filter/project forms.
+ * Integer columns and CONST_I64 stay in an exact int64 lane; an operation
+ * with a DOUBLE on either side coerces the other to double. Integer division
+ * truncates toward zero and integer `/ 0` is NULL (Trino raises; the ABI has
+ * no per-row error channel), so a projection with a DIV carries a validity
+ * bitmap even over NULL-free inputs. Integer overflow is undefined. AND / OR /
+ * NOT / BETWEEN are Kleene logic; a filter keeps a row iff the result is
+ * non-NULL and non-zero.
+ * Validation (host side, before anything is launched): a program must reduce
+ * to one value (else TG_ERR_INVALID_ARG) within 6 stack slots and use only
+ * the opcodes 0..16 (else TG_ERR_UNSUPPORTED: TG_EXPR_IN_I64 is reserved, not
+ * implemented); when a page arrives, every TG_EXPR_COL index must lie inside
+ * its channels (TG_ERR_INVALID_ARG), and a VARCHAR channel may only be named
+ * by a one-instruction identity projection (TG_ERR_UNSUPPORTED otherwise). */
 typedef enum {
     TG_EXPR_COL = 0,       /* push column[arg0] value */
     TG_EXPR_CONST_F64 = 1, /* push f64 constant */
@@ -104,7 +117,7 @@ typedef enum {
     TG_EXPR_EQ = 11, TG_EXPR_NE = 12,
     TG_EXPR_AND = 13, TG_EXPR_OR = 14, TG_EXPR_NOT = 15,
     TG_EXPR_BETWEEN = 16,  /* value, lo, hi on stack */
-    TG_EXPR_IN_I64 = 17    /* arg0 = count, followed by imm list (host side) */
+    TG_EXPR_IN_I64 = 17    /* reserved: rejected with TG_ERR_UNSUPPORTED */
 } tg_expr_op;
 
 typedef struct tg_expr_inst {
@@ -136,7 +149,10 @@ tg_status tg_filter_project_create(tg_session*,
     tg_operator** out);
 
 /* Standalone columnar filter: predicate -> selection vector
- * (ColumnarFilter.filterPositionsRange/List). Synchronous helper used by tests. */
+ * (ColumnarFilter.filterPositionsRange/List). Synchronous helper used by tests.
+ * A range selection must lie inside the page (TG_ERR_INVALID_ARG); a list's
+ * entries are echoed in list order. A DICTIONARY / RLE block is NULL at a row
+ * when its own bitmap or its dictionary's bitmap says so. */
 tg_status tg_filter_run(tg_session*, const tg_expr* filter, const tg_page* page,
                         const tg_selected* input_sel,
                         int32_t* out_positions, int32_t* out_count);
@@ -357,7 +373,11 @@ tg_status tg_tpch_part_name_flag(tg_session*, const uint8_t* d_name_ids,
  * create the probe-side scan with the bridge attached — the membership test
  * runs inside the scan's filter kernel after the static predicate. Best
  * effort like the reference: generic/multi-channel keys or ranges beyond
- * 2^33 skip the bitmap and the scan runs the static filter alone. */
+ * 2^33 skip the bitmap and the scan runs the static filter alone.
+ * df_key_channel must be an integer-typed channel of the probe page (BIGINT,
+ * INTEGER, DATE, SMALLINT, TINYINT or BOOLEAN, each read at its own width): a
+ * DOUBLE or VARCHAR channel makes add_input return TG_ERR_UNSUPPORTED, an
+ * index outside the page TG_ERR_INVALID_ARG. A NULL key fails the filter. */
 tg_status tg_join_bridge_request_bitmap(tg_join_bridge*);
 tg_status tg_filter_project_create_df(tg_session*, const tg_expr* filter,
     const tg_expr* projections, const int32_t* proj_out_types, int32_t n_proj,
@@ -444,7 +464,15 @@ tg_status tg_device_malloc(tg_session*, void** out, int64_t bytes);
 tg_status tg_device_free(tg_session*, void* p);
 
 /* ---- TopN (operator/TopNOperator.java): ORDER BY ... LIMIT ----
- * sort_desc[i]: 0 = ASC (nulls last), 1 = DESC (nulls first) */
+ * sort_desc[i]: 0 = ASC (nulls last), 1 = DESC (nulls first).
+ * DOUBLE keys order numerically with -0.0 == +0.0, and every NaN (either sign
+ * bit, any payload) ranks as the single largest non-NULL value (Trino's
+ * ORDER BY rule): ASC ... +inf, NaN, NULL; DESC NULL, NaN, +inf ... NULL is
+ * ordered apart from every value, INT64_MAX and NaN included. Order among
+ * rows whose whole sort key ties is unspecified. Every output channel carries
+ * its rows' validity. Channels are fixed-width: a VARCHAR channel is rejected
+ * with TG_ERR_UNSUPPORTED, a sort channel outside the channels and a page
+ * whose cell widths differ from `types` with TG_ERR_INVALID_ARG. */
 tg_status tg_topn_create(tg_session*,
     const int32_t* types, int32_t n_channels,
     const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,

@@ -592,3 +592,232 @@ class TestJoinMatrixHost:
             assert [c.kind for c in build] == ["i64", "i64", "f64", "i32", "date",
                                                "i16", "i8", "str", "i64"]
             assert all((c.valid is not None) == src_nulls for c in build[1:-1])
+
+
+class TestFilterMatrixHost:
+    """Host-side checks for tests/test_gpu_filter_matrix.py: ref_eval gives
+    hand-computed answers, the size constants equal the ones parsed from the
+    sources, and every program that claims a path takes it by construction.
+    No GPU."""
+
+    @staticmethod
+    def mx():
+        import test_gpu_filter_matrix as m
+        return m
+
+    def test_constants_match_sources(self):
+        m = self.mx()
+        k = m.source_constants()
+        assert (k["CHUNK"], k["FSCAN_CHUNK"], k["FTERM_MAX"], k["MAX_STACK"]) == \
+            (m.CHUNK, m.FSCAN_CHUNK, m.FTERM_MAX, m.MAX_STACK)
+        assert k["TG_BLOCK"] * k["TG_MAX_BLOCKS"] == m.GRID_THREADS
+        assert m.GRID_N == m.GRID_THREADS + 257
+        assert k["SCAN_SMALL_FACTOR"] == 2
+        small = k["SCAN_SMALL_FACTOR"] * k["FSCAN_CHUNK"]
+        assert m.VARCHAR_COUNTS == (0, 1, small, small + 1, small + k["FSCAN_CHUNK"] + 1)
+        assert max(m.EDGE_SIZES) // m.CHUNK + 1 <= small     # chunk scans stay one launch
+        assert m.EDGE_SIZES == (0, 1, 63, 64, 65, m.CHUNK - 1, m.CHUNK, m.CHUNK + 1,
+                                2 * m.CHUNK + 7)
+        sizes = m.edge_sizes()
+        assert len(set(sizes)) == len(sizes)
+        for n in m.EDGE_SIZES:
+            assert n in sizes
+            assert n < 63 or any(s % 8 and 0 <= s - n <= 3 for s in sizes)
+
+    def test_kleene_truth_tables(self):
+        m = self.mx()
+        T, Fa, N = 1, 0, None
+        C, ev = m.C, m.ref_eval
+
+        def tri(prog, row):
+            v = ev(prog, row)
+            return None if v[2] else bool(v[0])
+
+        and_ = {(T, T): True, (T, Fa): False, (Fa, T): False, (Fa, Fa): False,
+                (T, N): None, (N, T): None, (Fa, N): False, (N, Fa): False, (N, N): None}
+        or_ = {(T, T): True, (T, Fa): True, (Fa, T): True, (Fa, Fa): False,
+               (T, N): True, (N, T): True, (Fa, N): None, (N, Fa): None, (N, N): None}
+        for (a, b), want in and_.items():
+            assert tri((C(0), C(1), "and"), (a, b)) is want, (a, b)
+        for (a, b), want in or_.items():
+            assert tri((C(0), C(1), "or"), (a, b)) is want, (a, b)
+        assert [tri((C(0), "not"), (a,)) for a in (T, Fa, N)] == [False, True, None]
+        # a filter keeps a row iff the result is non-NULL and truthy
+        assert [m.ref_keep((C(0),), (a,)) for a in (T, Fa, N, 2.5, 0.0, -0.0)] == \
+            [True, False, False, True, False, False]
+
+    def test_division_and_coercion(self):
+        m = self.mx()
+        C, I, F, ev = m.C, m.I, m.F, m.ref_eval
+        assert ev((C(0), C(1), "div"), (7, 2)) == (3, True, False)
+        assert ev((C(0), C(1), "div"), (-7, 2)) == (-3, True, False)     # toward zero
+        assert ev((C(0), C(1), "div"), (7, -2)) == (-3, True, False)
+        assert ev((C(0), C(1), "div"), (7, 0))[2] is True                # int / 0 = NULL
+        assert ev((C(0), C(1), "div"), (None, 0))[2] is True
+        assert ev((C(0), C(1), "div"), (7.0, 0)) == (float("inf"), False, False)
+        assert ev((C(0), C(1), "div"), (-7, 0.0)) == (float("-inf"), False, False)
+        assert ev((C(0), C(1), "div"), (7.0, -0.0)) == (float("-inf"), False, False)
+        v = ev((C(0), C(1), "div"), (0.0, 0))
+        assert v[0] != v[0] and not v[2]
+        # mixed int/double coerces with float(i): 2^53+1 rounds to 2^53
+        big = 2 ** 53 + 1
+        assert ev((C(0), F(float(2 ** 53)), "eq"), (big,)) == (1, True, False)
+        assert ev((C(0), I(2 ** 53), "eq"), (big,)) == (0, True, False)  # exact lane
+        assert ev((C(0), F(0.0), "add"), (big,)) == (float(2 ** 53), False, False)
+        assert ev((C(0), I(1), "add"), (big,)) == (big + 1, True, False)
+        with pytest.raises(m.LeftInt64):
+            ev((C(0), C(0), "mul"), (2 ** 32,))
+
+    def test_nan_compares_and_between(self):
+        m = self.mx()
+        C, ev = m.C, m.ref_eval
+        nan = float("nan")
+        for op in m.CMPS:
+            want = 1 if op == "ne" else 0
+            assert ev((C(0), C(1), op), (nan, 1.0)) == (want, True, False), op
+            assert ev((C(0), C(1), op), (1, nan)) == (want, True, False), op
+            assert ev((C(0), C(1), op), (nan, nan)) == (want, True, False), op
+        assert ev((C(0), C(1), "eq"), (0.0, -0.0))[0] == 1
+
+        def btw(a, lo, hi):
+            v = ev((C(0), C(1), C(2), "between"), (a, lo, hi))
+            return None if v[2] else bool(v[0])
+
+        assert btw(5, 1, 9) is True and btw(5, 6, 9) is False and btw(5, 9, 1) is False
+        assert btw(5, None, 9) is None and btw(5, 1, None) is None
+        assert btw(5, None, 4) is False and btw(5, 6, None) is False     # false dominates
+        assert btw(None, 1, 9) is None and btw(5, None, None) is None
+        assert btw(5, 1, nan) is False and btw(nan, 1, 9) is False
+        assert btw(2 ** 53 + 1, float(2 ** 53), 2 ** 53 + 1) is True
+
+    def test_path_claims_hold_by_construction(self):
+        m = self.mx()
+        cap = m.source_constants()["FTERM_MAX"]
+        wide = m.chain(*m.WIDE)
+        assert len(m.WIDE) == cap + 1 and m.count_terms(wide) == cap + 1
+        assert m.path_of(wide) == "flags"
+        assert m.count_terms(m.chain(*m.WIDE[:cap])) == cap
+        n_terms = n_miss = 0
+        for prog, path in m.terms_programs():
+            assert m.path_of(prog) == path, prog
+            assert m.stack_profile(prog)[1:] == (1, False)
+            if path == "terms":
+                n_terms += 1
+            elif prog != wide:
+                n_miss += 1
+                assert m.count_terms(prog) == 0, prog      # really breaks the grammar
+        assert n_terms >= 20 and n_miss >= 5
+        for prog in m.flags_programs():
+            assert m.path_of(prog) == "flags", prog
+            mx_, sp, under = m.stack_profile(prog)
+            assert mx_ <= m.MAX_STACK and sp == 1 and not under
+        assert max(m.stack_profile(p)[0] for p in m.flags_programs()) == m.MAX_STACK
+        assert m.stack_profile(m.deep_program(m.MAX_STACK + 1))[0] == m.MAX_STACK + 1
+        for name, prog in m.GRID_FILTERS:
+            assert m.path_of(prog) == name
+        for prog in m.EDGE_PROGS:
+            assert m.ref_filter(prog, [(1,), (0,), (1,)]) == [0, 2]
+        assert [m.path_of(p) for p in m.EDGE_PROGS] == ["cmp", "terms", "flags"]
+
+    def test_random_programs_stay_in_int64_and_select(self):
+        m = self.mx()
+        assert len(m.RANDOM_SEEDS) == 64 == len(set(m.RANDOM_SEEDS))
+        cols, rows = m.random_page()
+        assert [c.kind for c in cols] == list(m.KINDS)
+        assert all(c.valid is not None and not c.valid.all() for c in cols)
+        for c in cols:
+            assert np.abs(c.values).max() < 2 ** 31
+        useful = 0
+        for seed in m.RANDOM_SEEDS:
+            prog, kept = m.random_reference(seed)          # raises LeftInt64 on overflow
+            mx_, sp, under = m.stack_profile(prog)
+            assert mx_ <= m.MAX_STACK and sp == 1 and not under, seed
+            for it in prog:
+                if isinstance(it, tuple) and it[0] != "col":
+                    assert abs(it[1]) <= 2 ** 31
+            useful += 0.05 <= len(kept) / len(rows) <= 0.95
+        assert useful >= len(m.RANDOM_SEEDS) // 4, useful
+
+    def test_patterns(self):
+        m = self.mx()
+        n = 2 * m.CHUNK + 7
+        assert m.pattern_flags("lane63", n).sum() == n // 64
+        last = np.flatnonzero(m.pattern_flags("chunk_last", n))
+        assert last.tolist() == [m.CHUNK - 1, 2 * m.CHUNK - 1, n - 1]
+        a, b = m.pattern_flags("first_chunk_only", n), m.pattern_flags("second_chunk_only", n)
+        assert a[:m.CHUNK].all() and not a[m.CHUNK:].any()
+        assert b[m.CHUNK:2 * m.CHUNK].all() and not b[:m.CHUNK].any() and not b[2 * m.CHUNK:].any()
+
+
+class TestOrderingMatrixHost:
+    """Host-side checks for tests/test_gpu_ordering_matrix.py: the TopN
+    reference by hand, the page shapes against the parsed path threshold and
+    the partitioner shape list. No GPU."""
+
+    @staticmethod
+    def mx():
+        import test_gpu_ordering_matrix as m
+        return m
+
+    def test_ref_topn_by_hand(self):
+        m = self.mx()
+        nan, inf = float("nan"), float("inf")
+        keys = [(1.0,), (None,), (nan,), (-0.0,), (0.0,), (-nan,), (inf,), (-inf,), (None,)]
+        asc = [m.canon_key(keys[i]) for i in m.ref_topn(keys, [0], 99)]
+        assert asc == [(-inf,), (0.0,), (0.0,), (1.0,), (inf,), ("nan",), ("nan",),
+                       (None,), (None,)]
+        desc = [m.canon_key(keys[i]) for i in m.ref_topn(keys, [1], 99)]
+        assert desc == asc[::-1]
+        assert m.ref_topn(keys, [0], 3)[0] == 7 and len(m.ref_topn(keys, [0], 3)) == 3
+        # ties on the leading key are broken by the second, each in its direction
+        keys = [(2, 1.0), (1, nan), (2, None), (1, 5.0), (None, 0.0), (2, -3.0)]
+        assert m.ref_topn(keys, [0, 0], 6) == [3, 1, 5, 0, 2, 4]
+        assert m.ref_topn(keys, [0, 1], 6) == [1, 3, 2, 0, 5, 4]
+        assert m.ref_topn(keys, [1, 0], 6) == [4, 5, 0, 2, 3, 1]
+        assert m.ref_topn(keys, [0, 0], 2) == [3, 1]
+        # INT64 extremes stay apart from NULL
+        big = [(2 ** 63 - 1,), (None,), (-2 ** 63,)]
+        assert m.ref_topn(big, [0], 3) == [2, 0, 1] and m.ref_topn(big, [1], 3) == [1, 0, 2]
+        assert m.canon_key((-0.0, None, -nan, 3)) == (0.0, None, "nan", 3)
+
+    def test_topn_shapes_hit_the_threshold(self):
+        m = self.mx()
+        k = m.source_constants()
+        assert k["TOPN_DEVICE_ROWS"] == m.TOPN_DEVICE_ROWS == m.PATH_ROWS["device"]
+        assert m.PATH_ROWS["host"] == 1000 < k["TOPN_DEVICE_ROWS"]
+        assert m.page_sizes(m.TOPN_DEVICE_ROWS) == (1, 0, k["TOPN_DEVICE_ROWS"] - 2, 1)
+        assert sum(m.page_sizes(m.TOPN_DEVICE_ROWS)) == k["TOPN_DEVICE_ROWS"]
+        assert sum(m.page_sizes(m.TOPN_DEVICE_ROWS - 1)) == k["TOPN_DEVICE_ROWS"] - 1
+        assert sum(m.page_sizes(m.HOST_ROWS)) == 1000
+        for name in ("int64_extremes", "double_specials", "all_ones_nan"):
+            c = m.special_cols(name, 1000, 12)
+            assert 100 < (~c.valid).sum() < 400
+        bits = m.special_cols("all_ones_nan", 1000, 12).values.view(np.uint64)
+        assert (bits == 0x7FFFFFFFFFFFFFFF).any()
+        d = m.special_cols("double_specials", 1000, 12).values
+        assert np.isnan(d).any() and (np.signbit(d) & np.isnan(d)).any()
+        assert (np.signbit(d) & (d == 0)).any() and (~np.signbit(d) & (d == 0)).any()
+        ext = m.special_cols("int64_extremes", 1000, 12).values
+        assert ext.max() == 2 ** 63 - 1 and ext.min() == -2 ** 63
+
+    def test_partition_shapes(self):
+        m = self.mx()
+        k = m.source_constants()
+        assert (k["PCHUNK"], k["MAX_PARTS"]) == (m.PCHUNK, m.MAX_PARTS)
+        assert k["RETIRED"] == 2
+        shapes = m.partition_shapes()
+        assert len(shapes) == len(set(shapes)) == 48
+        assert set(shapes) == {(n, p) for n in (0, 1, 64, 65, k["PCHUNK"] - 1, k["PCHUNK"],
+                                                k["PCHUNK"] + 1, 2 * k["PCHUNK"] + 1)
+                               for p in (1, 2, 63, 64, 65, k["MAX_PARTS"])}
+
+    def test_ref_split_is_stable_and_uses_the_oracle(self):
+        m = self.mx()
+        cols = m.part_cols(500, 3)
+        pids = m.ref_partition_ids(cols[:1], 7)
+        h = oracle.hash_rows([cols[0].values], [oracle.TG_BIGINT])
+        assert pids.tolist() == [oracle.partition_remote(int(np.int64(x)), 7) for x in h]
+        parts = m.ref_split(pids, 7)
+        assert sorted(i for p in parts for i in p) == list(range(500))
+        assert all(p == sorted(p) for p in parts)
+        assert all(pids[i] == q for q, p in enumerate(parts) for i in p)

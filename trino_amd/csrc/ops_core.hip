@@ -22,6 +22,29 @@ __global__ void k_rle_decode(const T* __restrict__ value, int64_t n, T* __restri
     for (; i < n; i += stride) out[i] = v;
 }
 
+/* validity of a decoded dictionary/RLE block: row i is valid iff the block's
+ * own bitmap says so AND the dictionary entry it names is valid (ids ==
+ * nullptr: RLE, every row names entry 0). One thread per output word. */
+__global__ void k_dict_valid(const uint64_t* __restrict__ outer,
+                             const uint64_t* __restrict__ dict_valid,
+                             const int32_t* __restrict__ ids, int64_t n,
+                             uint64_t* __restrict__ out)
+{
+    int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t words = (n + 63) / 64;
+    for (; w < words; w += stride) {
+        uint64_t bits = 0;
+        for (int b = 0; b < 64; b++) {
+            int64_t i = w * 64 + b;
+            if (i >= n) break;
+            int64_t id = ids ? ids[i] : 0;
+            bits |= ((dict_valid[id >> 6] >> (id & 63)) & 1ull) << b;
+        }
+        out[w] = outer ? (bits & outer[w]) : bits;
+    }
+}
+
 tg_status upload_flat(tg_session* s, const void* src, int on_device,
                       int64_t bytes, void** out)
 {
@@ -126,6 +149,32 @@ tg_status tg_upload_page(tg_session* s, const tg_page* in, DevPage* out)
                 default: st = decode_to_flat<int8_t>(s, b, db); break;
             }
             if (st != TG_OK) return st;
+            if (b->dictionary && b->dictionary->valid) {
+                /* NULL dictionary entries: fold them into the row bitmap */
+                const tg_block* d = b->dictionary;
+                int64_t words = (db->n + 63) / 64;
+                int64_t nd = b->kind == TG_BK_DICTIONARY ? d->position_count : 1;
+                uint64_t* d_dv = nullptr; uint64_t* d_outer = nullptr; int32_t* d_ids = nullptr;
+                st = upload_flat(s, d->valid, d->on_device, ((nd + 63) / 64) * 8, (void**)&d_dv);
+                if (st != TG_OK) return st;
+                if (b->kind == TG_BK_DICTIONARY) {
+                    st = upload_flat(s, b->ids, b->on_device, db->n * 4, (void**)&d_ids);
+                    if (st != TG_OK) return st;
+                }
+                if (b->valid) {
+                    st = upload_flat(s, b->valid, b->on_device, words * 8, (void**)&d_outer);
+                    if (st != TG_OK) return st;
+                }
+                TG_POOL_ALLOC(s, &db->valid, (words ? words : 1) * 8);
+                hipLaunchKernelGGL(k_dict_valid, dim3(tg_grid_for(words)), dim3(TG_BLOCK), 0,
+                                   s->stream, d_outer, d_dv, d_ids, db->n, db->valid);
+                TG_HIP_CHECK(hipGetLastError());
+                TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+                tg_pool_free(s, d_dv);
+                if (d_ids) tg_pool_free(s, d_ids);
+                if (d_outer) tg_pool_free(s, d_outer);
+                continue;
+            }
         }
         if (b->valid) {
             if (b->on_device) {

@@ -10,7 +10,8 @@
  *    specialization, CallColumnarFilterGenerator.java:160-198);
  *  - PageProjection.project over SelectedPositions (project/PageProcessor.
  *    java:274-305); per-query bytecode gen is replaced by a device postfix
- *    interpreter over the tg_expr IR (stack depth <= 4, checked at compile).
+ *    interpreter over the tg_expr IR (stack depth <= MAX_STACK, opcodes and
+ *    column indices checked on the host before any launch).
  */
 #include "operators.h"
 #include <cstdlib>
@@ -27,8 +28,13 @@ __device__ static inline bool df_test(const DF& df, const KCol* cols, int64_t i)
     if (!df.bm) return true;
     const KCol& c = cols[df.col];
     if (c.valid && !((c.valid[i >> 6] >> (i & 63)) & 1)) return false;
-    int64_t k = (c.type == TG_BIGINT) ? ((const int64_t*)c.data)[i]
-                                      : (int64_t)((const int32_t*)c.data)[i];
+    int64_t k;   /* DOUBLE/VARCHAR key channels are rejected on the host */
+    switch (c.type) {
+        case TG_BIGINT: k = ((const int64_t*)c.data)[i]; break;
+        case TG_SMALLINT: k = ((const int16_t*)c.data)[i]; break;
+        case TG_TINYINT: case TG_BOOLEAN: k = ((const int8_t*)c.data)[i]; break;
+        default: k = ((const int32_t*)c.data)[i]; break;
+    }
     if (k < df.mn || k > df.mx) return false;
     int64_t b = k - df.mn;
     return (df.bm[b >> 6] >> (b & 63)) & 1;
@@ -788,7 +794,7 @@ __global__ void k_gather_var_lens(const int32_t* __restrict__ src_off,
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        int32_t p = pos[i];
+        int64_t p = pos ? (int64_t)pos[i] : i;   /* null = identity (no filter) */
         bool isnull = p < 0 ||
                       (src_valid && !((src_valid[p >> 6] >> (p & 63)) & 1));
         lens[i] = isnull ? 0 : src_off[p + 1] - src_off[p];
@@ -807,8 +813,9 @@ __global__ void k_gather_var_bytes(const uint8_t* __restrict__ src_bytes,
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
         int32_t len = out_off[i + 1] - out_off[i];
-        if (pos[i] < 0) continue;   /* null: zero-length */
-        const uint8_t* sp = src_bytes + src_off[pos[i]];
+        int64_t p = pos ? (int64_t)pos[i] : i;   /* null = identity (no filter) */
+        if (p < 0) continue;   /* null: zero-length */
+        const uint8_t* sp = src_bytes + src_off[p];
         uint8_t* dp = out_bytes + out_off[i];
         for (int32_t b = 0; b < len; b++) dp[b] = sp[b];
     }
@@ -934,6 +941,15 @@ __global__ void k_proj_cmp_flag(KCol col, int op, double cval, int64_t icval,
     }
 }
 
+/* an integer `/ 0` yields NULL, so a program with a DIV needs an output
+ * bitmap even over NULL-free inputs */
+static bool expr_has_div(const ExprProgram& e)
+{
+    for (int i = 0; i < e.count; i++)
+        if (e.insts[i].op == TG_EXPR_DIV) return true;
+    return false;
+}
+
 tg_status run_project(tg_session* s, const ExprProgram& proj, tg_type out_type,
                       const DevPage& page, const int32_t* d_positions, int32_t count,
                       DevBlock* out)
@@ -990,7 +1006,7 @@ tg_status run_project(tg_session* s, const ExprProgram& proj, tg_type out_type,
     }
 
     std::vector<KCol> cols(page.blocks.size());
-    bool any_null = false;
+    bool any_null = expr_has_div(proj);
     for (size_t i = 0; i < page.blocks.size(); i++) {
         cols[i] = {page.blocks[i].data, page.blocks[i].valid, (int32_t)page.blocks[i].type, 0};
         any_null |= page.blocks[i].valid != nullptr;
@@ -1017,6 +1033,28 @@ tg_status run_project(tg_session* s, const ExprProgram& proj, tg_type out_type,
     return TG_OK;
 }
 
+/* every column an expression names must exist in the page, and only an
+ * identity projection may name a VARCHAR channel (the interpreter would read
+ * its bytes as double). Host-side, before anything is uploaded or launched. */
+static tg_status check_expr_page(const ExprProgram& e, const tg_page* page,
+                                 bool allow_identity)
+{
+    for (int i = 0; i < e.count; i++) {
+        if (e.insts[i].op != TG_EXPR_COL) continue;
+        int32_t c = e.insts[i].arg0;
+        if (c < 0 || c >= page->channel_count) {
+            TG_SET_ERR("expr column index %d outside the page's %d channels",
+                       c, page->channel_count);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (page->blocks[c].type == TG_VARCHAR && !(allow_identity && e.count == 1)) {
+            TG_SET_ERR("VARCHAR channel %d in a compare or arithmetic expression", c);
+            return TG_ERR_UNSUPPORTED;
+        }
+    }
+    return TG_OK;
+}
+
 /* ---- FilterAndProject operator ---- */
 bool tg_bridge_df(tg_join_bridge* b, const uint64_t** bm, int64_t* mn, int64_t* mx);
 
@@ -1036,9 +1074,31 @@ struct FilterProjectOp : tg_operator {
          * evaluation) against grid-stride flag+gather kernels. Default stays
          * unfused; the fused path needs a block-parallel write design
          *  before it can win. */
-        static int fused = [] { const char* e = getenv("TG_FP_FUSED"); return e ? atoi(e) : 0; }();
+        static int fused_env = [] { const char* e = getenv("TG_FP_FUSED"); return e ? atoi(e) : 0; }();
+        tg_status st = TG_OK;
+        if (has_filter) st = check_expr_page(filter, page, false);
+        for (size_t p = 0; st == TG_OK && p < projections.size(); p++)
+            st = check_expr_page(projections[p], page, true);
+        if (st != TG_OK) return st;
+        if (df_bridge) {
+            if (df_channel < 0 || df_channel >= page->channel_count) {
+                TG_SET_ERR("dynamic filter key channel %d outside the page's %d channels",
+                           df_channel, page->channel_count);
+                return TG_ERR_INVALID_ARG;
+            }
+            if (!type_is_int(page->blocks[df_channel].type)) {
+                TG_SET_ERR("dynamic filter key channel %d is not an integer type", df_channel);
+                return TG_ERR_UNSUPPORTED;
+            }
+        }
+        /* the fused kernels know neither the dynamic filter nor VARCHAR
+         * columns: such pages take the selection-vector path */
+        bool fused = fused_env != 0 && !df_bridge;
+        for (auto& p : projections)
+            if (p.count == 1 && p.insts[0].op == TG_EXPR_COL &&
+                page->blocks[p.insts[0].arg0].type == TG_VARCHAR) fused = false;
         DevPage in;
-        tg_status st = tg_upload_page(s, page, &in);
+        st = tg_upload_page(s, page, &in);
         if (st != TG_OK) return st;
         DF df{nullptr, 0, 0, 0, 0};
         bool have_df = false;
@@ -1113,6 +1173,7 @@ struct FilterProjectOp : tg_operator {
         std::vector<KProj> kp(projections.size());
         bool any_null = false;
         for (auto& b : in.blocks) any_null |= b.valid != nullptr;
+        for (auto& p : projections) any_null |= expr_has_div(p);
         for (size_t p = 0; p < projections.size(); p++) {
             DevBlock& ob = outp.blocks[p];
             bool ident = projections[p].count == 1 &&
@@ -1165,7 +1226,18 @@ struct FilterProjectOp : tg_operator {
 static tg_status check_expr_depth(const tg_expr* e)
 {
     int sp = 0, maxsp = 0;
+    if (!e->insts || e->count < 1) { TG_SET_ERR("empty expr"); return TG_ERR_INVALID_ARG; }
     for (int i = 0; i < e->count; i++) {
+        int op = e->insts[i].op;
+        /* TG_EXPR_IN_I64 is declared in the header but not implemented */
+        if (op < TG_EXPR_COL || op > TG_EXPR_BETWEEN) {
+            TG_SET_ERR("expr opcode %d at inst %d is not implemented", op, i);
+            return TG_ERR_UNSUPPORTED;
+        }
+        if (op == TG_EXPR_COL && e->insts[i].arg0 < 0) {
+            TG_SET_ERR("expr column index %d at inst %d", e->insts[i].arg0, i);
+            return TG_ERR_INVALID_ARG;
+        }
         switch (e->insts[i].op) {
             case TG_EXPR_COL: case TG_EXPR_CONST_F64: case TG_EXPR_CONST_I64: sp++; break;
             case TG_EXPR_NOT: break;
@@ -1330,6 +1402,18 @@ extern "C" tg_status tg_filter_run(tg_session* s, const tg_expr* filter, const t
     tg_status st = check_expr_depth(filter);
     if (st != TG_OK) return st;
     ExprProgram prog;
+    prog.insts.assign(filter->insts, filter->insts + filter->count);
+    prog.count = filter->count;
+    st = check_expr_page(prog, page, false);
+    if (st != TG_OK) return st;
+    if (input_sel && (input_sel->size < 0 || (input_sel->is_list && input_sel->size > 0 &&
+                                              !input_sel->positions) ||
+                      (!input_sel->is_list &&
+                       (input_sel->offset < 0 ||
+                        (int64_t)input_sel->offset + input_sel->size > page->position_count)))) {
+        TG_SET_ERR("selection outside the page");
+        return TG_ERR_INVALID_ARG;
+    }
     st = tg_compile_expr(s, filter, &prog);
     if (st != TG_OK) return st;
     /* dictionary-aware path: single-channel predicate over a fixed-width
@@ -1340,6 +1424,9 @@ extern "C" tg_status tg_filter_run(tg_session* s, const tg_expr* filter, const t
         page->blocks[fc].kind == TG_BK_DICTIONARY &&
         page->blocks[fc].dictionary &&
         page->blocks[fc].dictionary->type != TG_VARCHAR &&
+        /* a bitmap on either level takes the decoded path, which combines
+         * the block's own bitmap with the dictionary's */
+        !page->blocks[fc].valid &&
         !page->blocks[fc].dictionary->valid) {
         int32_t* d_pos = nullptr;
         int32_t count = 0;

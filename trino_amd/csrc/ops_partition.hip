@@ -226,7 +226,7 @@ struct PagePartitionerOp : tg_operator {
             tg_block tb{};
             tb.type = b.type; tb.kind = TG_BK_VALUE;
             tb.position_count = pg.n; tb.on_device = 1;
-            tb.data = b.data; tb.valid = b.valid;
+            tb.data = b.data; tb.valid = b.valid; tb.offsets = b.offsets;
             out_blocks_.push_back(tb);
         }
         out->channel_count = (int32_t)pg.blocks.size();

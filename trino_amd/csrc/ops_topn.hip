@@ -15,10 +15,13 @@
 #include <algorithm>
 
 /* order-preserving map to an unsigned "ascending sortable" key space:
- * integers: flip the sign bit; doubles: IEEE total-order trick. DESC
- * channels are stored bit-inverted so every radix pass sorts ascending;
- * nulls map to the extreme that lands them last (ASC) / first (DESC),
- * Trino's default null ordering. */
+ * integers: flip the sign bit; doubles: IEEE total-order trick after
+ * canonicalising -0.0 to +0.0 and every NaN (either sign bit) to one quiet
+ * NaN, so +-0 tie and all NaNs tie as the largest non-NULL value (Trino's
+ * ORDER BY rule; the host comparator below agrees). DESC channels are stored
+ * bit-inverted so every radix pass sorts ascending. NULLs are ordered by a
+ * separate stable 1-bit pass (k_topn_null_keys): every u64 image belongs to
+ * some value (INT64_MAX, NaN), so no in-band sentinel exists. */
 __device__ static inline uint64_t topn_sortable(const void* data, int32_t type, int64_t i)
 {
     const uint64_t SIGN = 0x8000000000000000ull;
@@ -30,7 +33,10 @@ __device__ static inline uint64_t topn_sortable(const void* data, int32_t type, 
         case TG_TINYINT: case TG_BOOLEAN:
             return (uint64_t)(int64_t)((const int8_t*)data)[i] ^ SIGN;
         default: {
-            long long b = __double_as_longlong(((const double*)data)[i]);
+            double v = ((const double*)data)[i];
+            if (v != v) return 0x7FF8000000000000ull | SIGN;   /* one NaN */
+            if (v == 0.0) v = 0.0;                               /* -0.0 -> +0.0 */
+            long long b = __double_as_longlong(v);
             return b < 0 ? ~(uint64_t)b : ((uint64_t)b | SIGN);
         }
     }
@@ -45,12 +51,44 @@ __global__ void k_topn_keys(const void* __restrict__ data,
     for (; i < n; i += stride) {
         bool isnull = valid && !((valid[i >> 6] >> (i & 63)) & 1);
         uint64_t key;
-        if (isnull) key = desc ? 0ull : ~0ull;
+        if (isnull) key = 0ull;   /* placed by the null pass */
         else {
             key = topn_sortable(data, type, i);
             if (desc) key = ~key;
         }
         out[i] = key;
+    }
+}
+
+/* 1-bit key of the null pass: ASC nulls last (1), DESC nulls first (0) */
+__global__ void k_topn_null_keys(const uint64_t* __restrict__ valid, int32_t desc,
+                                 int64_t n, uint64_t* __restrict__ out)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        bool isnull = valid && !((valid[i >> 6] >> (i & 63)) & 1);
+        out[i] = (isnull != (desc != 0)) ? 1ull : 0ull;
+    }
+}
+
+/* output gather of one source page: output slot o takes flat row idx[o] when
+ * it lies in this page ([base, base + n)); a NULL source cell clears the
+ * output's validity bit */
+template <typename T>
+__global__ void k_topn_gather(const T* __restrict__ src, const uint64_t* __restrict__ src_valid,
+                              const int64_t* __restrict__ idx, int64_t take,
+                              int64_t base, int64_t n, T* __restrict__ out,
+                              uint64_t* __restrict__ out_valid)
+{
+    int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; o < take; o += stride) {
+        int64_t r = idx[o] - base;
+        if (r < 0 || r >= n) continue;
+        out[o] = src[r];
+        if (src_valid && !((src_valid[r >> 6] >> (r & 63)) & 1))
+            atomicAnd((unsigned long long*)&out_valid[o >> 6], ~(1ull << (o & 63)));
     }
 }
 
@@ -81,6 +119,21 @@ struct TopNOp : tg_operator {
 
     tg_status add_input(const tg_page* page) override
     {
+        /* the output gather copies cells at the declared width */
+        if (page->channel_count < (int32_t)types.size()) {
+            TG_SET_ERR("topn page has %d channels, operator %zu", page->channel_count, types.size());
+            return TG_ERR_INVALID_ARG;
+        }
+        for (size_t c = 0; c < types.size(); c++) {
+            DevBlock want, got;
+            want.type = types[c];
+            got.type = (tg_type)page->blocks[c].type;
+            if (got.type == TG_VARCHAR || got.elem_size() != want.elem_size()) {
+                TG_SET_ERR("topn channel %zu type %d, operator declared %d", c,
+                           page->blocks[c].type, (int)types[c]);
+                return TG_ERR_INVALID_ARG;
+            }
+        }
         DevPage in;
         tg_status st = tg_upload_page(s, page, &in);
         if (st != TG_OK) return st;
@@ -106,9 +159,12 @@ struct TopNOp : tg_operator {
         std::vector<int64_t> page_base(pages.size() + 1, 0);
         for (size_t p = 0; p < pages.size(); p++)
             page_base[p + 1] = page_base[p] + pages[p].n;
-        std::vector<uint64_t*> kf(k, nullptr);
+        std::vector<uint64_t*> kf(k, nullptr), nf(k, nullptr);
         for (size_t j = 0; j < k; j++) {
             TG_POOL_ALLOC(s, &kf[j], total_rows * 8);
+            bool nullable = false;
+            for (auto& pg : pages) nullable |= pg.n && pg.blocks[sort_channels[j]].valid;
+            if (nullable) TG_POOL_ALLOC(s, &nf[j], total_rows * 8);
             for (size_t p = 0; p < pages.size(); p++) {
                 const DevBlock& b = pages[p].blocks[sort_channels[j]];
                 if (!pages[p].n) continue;
@@ -116,6 +172,11 @@ struct TopNOp : tg_operator {
                                    dim3(TG_BLOCK), 0, s->stream, b.data, b.valid,
                                    (int32_t)b.type, sort_desc[j], pages[p].n,
                                    kf[j] + page_base[p]);
+                TG_HIP_CHECK(hipGetLastError());
+                if (!nullable) continue;
+                hipLaunchKernelGGL(k_topn_null_keys, dim3(tg_grid_for(pages[p].n)),
+                                   dim3(TG_BLOCK), 0, s->stream, b.valid,
+                                   sort_desc[j], pages[p].n, nf[j] + page_base[p]);
                 TG_HIP_CHECK(hipGetLastError());
             }
         }
@@ -133,13 +194,21 @@ struct TopNOp : tg_operator {
             TG_HIP_CHECK(hipGetLastError());
             tg_status st = run_sort_pairs(s, d_keys, d_perm, total_rows);
             if (st != TG_OK) return st;
+            if (!nf[j]) continue;
+            /* the channel's major order: NULL or not, one stable 1-bit pass */
+            hipLaunchKernelGGL(k_gather_u64_by_perm, dim3(tg_grid_for(total_rows)),
+                               dim3(TG_BLOCK), 0, s->stream, nf[j], d_perm,
+                               total_rows, d_keys);
+            TG_HIP_CHECK(hipGetLastError());
+            st = run_sort_pairs_bits(s, d_keys, d_perm, total_rows, 1);
+            if (st != TG_OK) return st;
         }
         idx->resize(take);
         if (take) {
             TG_HIP_CHECK(hipMemcpy(idx->data(), d_perm, take * 8,
                                    hipMemcpyDeviceToHost));
         }
-        for (size_t j = 0; j < k; j++) tg_pool_free(s, kf[j]);
+        for (size_t j = 0; j < k; j++) { tg_pool_free(s, kf[j]); tg_pool_free(s, nf[j]); }
         tg_pool_free(s, d_perm);
         tg_pool_free(s, d_keys);
         return TG_OK;
@@ -222,8 +291,12 @@ struct TopNOp : tg_operator {
                 }
                 int cmp;
                 if (types[sort_channels[j]] == TG_DOUBLE) {
+                    /* +-0 tie; every NaN ties with every NaN above +inf: a
+                     * strict weak ordering, the same as topn_sortable's */
                     double x = keys_f[j][a], y = keys_f[j][b];
-                    cmp = (x < y) ? -1 : (x > y) ? 1 : 0;
+                    bool xn = x != x, yn = y != y;
+                    cmp = (xn || yn) ? (int)xn - (int)yn
+                                     : (x < y) ? -1 : (x > y) ? 1 : 0;
                 }
                 else {
                     int64_t x = keys_i[j][a], y = keys_i[j][b];
@@ -243,12 +316,17 @@ struct TopNOp : tg_operator {
 
     tg_status gather_out(int64_t take, const std::vector<int64_t>& idx)
     {
-        /* map flat row -> (page, row) and gather per page (order preserved by
-         * gathering per output slot via int32 positions within each page) */
+        /* one gather launch per (channel, source page): each output slot
+         * finds its flat row in exactly one page; validity travels along */
         std::vector<int64_t> page_base(pages.size() + 1, 0);
         for (size_t p = 0; p < pages.size(); p++)
             page_base[p + 1] = page_base[p] + pages[p].n;
 
+        int64_t* d_idx = nullptr;
+        TG_POOL_ALLOC(s, &d_idx, (take ? take : 1) * 8);
+        if (take)
+            TG_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), take * 8,
+                                        hipMemcpyHostToDevice, s->stream));
         DevPage outp;
         outp.n = take;
         for (size_t c = 0; c < types.size(); c++) {
@@ -256,19 +334,38 @@ struct TopNOp : tg_operator {
             b.type = types[c];
             b.n = take;
             TG_POOL_ALLOC(s, &b.data, (take ? take : 1) * b.elem_size());
-            /* copy element by element via DtoD (take is small: <= limit) */
-            for (int64_t o = 0; o < take; o++) {
-                int64_t flat = idx[o];
-                size_t p = std::upper_bound(page_base.begin(), page_base.end(), flat) -
-                           page_base.begin() - 1;
-                int64_t row = flat - page_base[p];
-                TG_HIP_CHECK(hipMemcpyAsync((char*)b.data + o * b.elem_size(),
-                                            (char*)pages[p].blocks[c].data + row * b.elem_size(),
-                                            b.elem_size(), hipMemcpyDeviceToDevice, s->stream));
+            bool nullable = false;
+            for (auto& pg : pages) nullable |= pg.n && pg.blocks[c].valid;
+            if (nullable) {
+                int64_t words = (take + 63) / 64;
+                TG_POOL_ALLOC(s, &b.valid, (words ? words : 1) * 8);
+                TG_HIP_CHECK(hipMemsetAsync(b.valid, 0xFF, words * 8, s->stream));
+            }
+            for (size_t p = 0; take && p < pages.size(); p++) {
+                const DevBlock& sb = pages[p].blocks[c];
+                int64_t pn = pages[p].n;
+                if (!pn) continue;
+                dim3 grid(tg_grid_for(take)), block(TG_BLOCK);
+                switch (b.elem_size()) {
+                    case 8: hipLaunchKernelGGL(k_topn_gather<int64_t>, grid, block, 0, s->stream,
+                                (const int64_t*)sb.data, sb.valid, d_idx, take, page_base[p], pn,
+                                (int64_t*)b.data, b.valid); break;
+                    case 4: hipLaunchKernelGGL(k_topn_gather<int32_t>, grid, block, 0, s->stream,
+                                (const int32_t*)sb.data, sb.valid, d_idx, take, page_base[p], pn,
+                                (int32_t*)b.data, b.valid); break;
+                    case 2: hipLaunchKernelGGL(k_topn_gather<int16_t>, grid, block, 0, s->stream,
+                                (const int16_t*)sb.data, sb.valid, d_idx, take, page_base[p], pn,
+                                (int16_t*)b.data, b.valid); break;
+                    default: hipLaunchKernelGGL(k_topn_gather<int8_t>, grid, block, 0, s->stream,
+                                (const int8_t*)sb.data, sb.valid, d_idx, take, page_base[p], pn,
+                                (int8_t*)b.data, b.valid); break;
+                }
+                TG_HIP_CHECK(hipGetLastError());
             }
             outp.blocks.push_back(b);
         }
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        tg_pool_free(s, d_idx);
         stage_output(std::move(outp));
         for (auto& p : pages) tg_free_page(s, &p);
         pages.clear();
@@ -302,6 +399,18 @@ extern "C" tg_status tg_topn_create(tg_session* s,
         TG_SET_ERR("invalid topn spec");
         return TG_ERR_INVALID_ARG;
     }
+    for (int i = 0; i < n_sort; i++)
+        if (sort_channels[i] < 0 || sort_channels[i] >= n_channels) {
+            TG_SET_ERR("topn sort channel %d outside %d channels", sort_channels[i], n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+    /* the output gather moves fixed-width cells only: no plan needs a VARCHAR
+     * channel through TopN yet, so it is rejected rather than mangled */
+    for (int i = 0; i < n_channels; i++)
+        if (types[i] == TG_VARCHAR) {
+            TG_SET_ERR("topn: VARCHAR channel %d is not supported", i);
+            return TG_ERR_UNSUPPORTED;
+        }
     auto* op = new TopNOp();
     op->s = s;
     for (int i = 0; i < n_channels; i++) op->types.push_back((tg_type)types[i]);

@@ -567,14 +567,19 @@ def request_bitmap(bridge):
     _check(_lib.tg_join_bridge_request_bitmap(bridge._h))
 
 
-def page_with_dict(columns):
+def page_with_dict(columns, valids=None, dict_valids=None):
     """Build a page where entries may be numpy arrays (flat) or
     (dict_values_array, ids_int32_array) tuples for dictionary-encoded
-    channels (DictionaryBlock analog)."""
+    channels (DictionaryBlock analog). valids: optional packed uint64 bitmap
+    (bit=1 valid) or None per channel, over the channel's rows; dict_valids:
+    the same per channel over the entries of its dictionary."""
     blocks = (TgBlock * len(columns))()
     keep = []
     n = None
     for i, col in enumerate(columns):
+        v = valids[i] if valids else None
+        blocks[i].valid = v.ctypes.data if v is not None else None
+        keep.append(v)
         if isinstance(col, tuple):
             dvals, ids = col
             n = len(ids)
@@ -584,7 +589,9 @@ def page_with_dict(columns):
             d.position_count = len(dvals)
             d.on_device = 0
             d.data = dvals.ctypes.data
-            keep += [dvals, ids, d]
+            dv = dict_valids[i] if dict_valids else None
+            d.valid = dv.ctypes.data if dv is not None else None
+            keep += [dvals, ids, d, dv]
             blocks[i].type = d.type
             blocks[i].kind = 1            # TG_BK_DICTIONARY
             blocks[i].position_count = n
