@@ -228,12 +228,39 @@ tg_status tg_hash_builder_create(tg_session*, tg_join_bridge*,
  * nothing, itself included) — unlike grouping, where all NaNs are one key.
  * The probe's key channels must equal the build's in count and, position by
  * position, in type: add_input rejects anything else with
- * TG_ERR_INVALID_ARG (channel types arrive with the first page). */
+ * TG_ERR_INVALID_ARG (channel types arrive with the first page).
+ * join_type 2 = build-outer (RIGHT) and 3 = FULL (LookupJoinOperators
+ * buildOuter): the operator emits exactly what join_type 0, respectively 1,
+ * emits on the same inputs, and records on the bridge which build rows it
+ * matched; tg_lookup_outer_create then emits the build rows nobody matched.
+ * Such a recording operator is counted on the bridge from its creation until
+ * its tg_operator_finish or tg_operator_close, so the bridge must outlive
+ * it. Any other join_type is rejected with TG_ERR_INVALID_ARG. */
 tg_status tg_lookup_join_create_ex(tg_session*, tg_join_bridge*,
     const int32_t* probe_types, int32_t n_probe_channels,
     const int32_t* key_channels, int32_t n_key_channels,
     const int32_t* probe_output_channels, int32_t n_probe_output,
     int32_t join_type, tg_operator** out);
+/* Lookup-outer operator (operator/join/LookupOuterOperator.java): the source
+ * operator that completes a RIGHT or FULL join. It emits one row for every
+ * build row that no probe row matched, build rows whose key has a NULL or a
+ * NaN component included (they can never match). Channels are the lookup
+ * join's: first n_probe_output columns of the given types in which every
+ * cell is NULL (cleared validity bit, zero length for VARCHAR), then the
+ * bridge's build output channels gathered from the build row. Rows come in
+ * ascending global build row order in ONE page; when every build row was
+ * matched, or the build is empty, no page is produced and `finished` is set.
+ * The visited set is the union over all recording (join_type 2 or 3) lookup
+ * joins that share the bridge; a bridge nobody probed emits every build row.
+ * tg_operator_get_output returns TG_ERR_STATE while the bridge is not built,
+ * while a recording lookup join on it is neither finished nor closed, or
+ * once a join_type 0 or 1 lookup join has probed it (its matches were not
+ * recorded), and TG_ERR_UNSUPPORTED on a set-builder bridge; all of this is
+ * checked before anything is launched. tg_operator_add_input returns
+ * TG_ERR_STATE and needs_input is 0. The bridge must outlive the operator. */
+tg_status tg_lookup_outer_create(tg_session*, tg_join_bridge*,
+    const int32_t* probe_output_types, int32_t n_probe_output,
+    tg_operator** out);
 tg_status tg_lookup_join_create(tg_session*, tg_join_bridge*,
     const int32_t* probe_types, int32_t n_probe_channels,
     const int32_t* key_channels, int32_t n_key_channels,

@@ -158,7 +158,23 @@ struct tg_join_bridge {
      * alongside the index and pushed into probe-side scan kernels. Best
      * effort like the reference: generic keys / huge ranges skip it. */
     bool want_bitmap = false;
+    /* build-outer (RIGHT / FULL) bookkeeping, the JoinBridge outer-position
+     * tracker analog: one visited bit per global build row, allocated and
+     * zeroed when the first recording probe operator (join_type 2 or 3) adds
+     * a page; `recording` counts such operators created and not yet finished
+     * or closed; `plain_probed` is set once a join_type 0 or 1 operator has
+     * probed, after which the visited set can no longer be complete. */
+    uint64_t* visited = nullptr;     /* [ceil(n / 64)] */
+    int32_t recording = 0;
+    bool plain_probed = false;
 };
+
+/* a bridge the positional operators cannot serve: the set builder's bitmap
+ * holds membership only, no rows */
+static bool bridge_is_set_only(const tg_join_bridge* b)
+{
+    return b->t.set_bitmap && !b->t.csr;
+}
 
 /* probe-side key channels must mirror the build's: same count and, per
  * position, the same type. The probe kernels index the probe KColH array by
@@ -763,6 +779,100 @@ static tg_status run_scan_counts(tg_session* s, const int32_t* d_counts, int64_t
     return TG_OK;
 }
 
+/* ---- build-outer (RIGHT / FULL): visited bitmap + unmatched-row emission
+ * (LookupJoinOperators buildOuter / LookupOuterOperator.java: the probe
+ * records the build positions it joined, the outer operator then emits the
+ * positions nobody visited) ---- */
+
+/* One pass over the matched build row list d_ob[0..total) that EVERY probe
+ * path of LookupJoinOp::add_input ends with, so recording is independent of
+ * the path that produced the list. -1 entries (FULL's probe-outer misses)
+ * are skipped. Wave-segmented like k_set_bits, for the same reason: the list
+ * is probe-row ordered, so a hot build row (millions of probes hitting one
+ * row, or the 500 copies of one key walked in descending row order) fills
+ * whole waves with the same bitmap WORD. Each equal-word run is OR-combined
+ * in registers, only the run's last lane looks at memory, and it skips the
+ * atomic when a plain load shows its bits already set (bits only ever go
+ * 0 -> 1 while probing, so a stale 0 costs one redundant atomic, never a
+ * lost bit). Measured on MI355X, join_type 2 against 0 on the same 2^20-row
+ * build and 2^22-row all-hit probe page (profiles/outer_join_mark_cost.txt):
+ * +0.026 ms on a 1.27 ms add_input (2 %) once the bits are set, +0.33 ms
+ * (25 %) on a fresh bitmap, where the scattered matches of a random probe
+ * order leave the wave combine nothing to merge. */
+__global__ void k_mark_visited(const int32_t* __restrict__ ob, int64_t total,
+                               uint64_t* __restrict__ visited)
+{
+    int lane = threadIdx.x % 64;
+    int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t iw = i0 - lane; iw < total; iw += stride) {
+        int64_t i = iw + lane;
+        int32_t row = i < total ? ob[i] : -1;
+        bool active = row >= 0;
+        int64_t w = -1;
+        uint64_t bit = 0;
+        if (active) {
+            w = row >> 6;
+            bit = 1ull << (row & 63);
+        }
+        /* inclusive OR-scan over equal-w prefixes */
+        #pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            uint64_t obit = __shfl_up(bit, off, 64);
+            int64_t ow = __shfl_up(w, off, 64);
+            if (lane >= off && ow == w) bit |= obit;
+        }
+        int64_t wnext = __shfl_down(w, 1, 64);
+        bool last = active && (lane == 63 || wnext != w);
+        if (last && (visited[w] & bit) != bit)
+            atomicOr((unsigned long long*)&visited[w], (unsigned long long)bit);
+    }
+}
+
+/* unvisited rows per bitmap word; the tail word is masked to n */
+__global__ void k_unvisited_count(const uint64_t* __restrict__ visited, int64_t n,
+                                  int32_t* __restrict__ counts)
+{
+    int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t words = (n + 63) / 64;
+    for (; w < words; w += stride) {
+        uint64_t mask = (w == words - 1 && (n & 63)) ? (1ull << (n & 63)) - 1 : ~0ull;
+        counts[w] = __popcll(~visited[w] & mask);
+    }
+}
+
+/* word w writes its unvisited rows, ascending, at offsets[w] */
+__global__ void k_unvisited_rows(const uint64_t* __restrict__ visited, int64_t n,
+                                 const int64_t* __restrict__ offsets,
+                                 int32_t* __restrict__ rows)
+{
+    int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t words = (n + 63) / 64;
+    for (; w < words; w += stride) {
+        uint64_t mask = (w == words - 1 && (n & 63)) ? (1ull << (n & 63)) - 1 : ~0ull;
+        uint64_t open = ~visited[w] & mask;
+        int64_t at = offsets[w];
+        while (open) {
+            int b = __ffsll((unsigned long long)open) - 1;
+            rows[at++] = (int32_t)(w * 64 + b);
+            open &= open - 1;
+        }
+    }
+}
+
+/* allocate and zero the bridge's visited bitmap on first need */
+static tg_status bridge_ensure_visited(tg_join_bridge* b)
+{
+    if (b->visited) return TG_OK;
+    int64_t words = (b->t.n + 63) / 64;
+    if (words < 1) words = 1;
+    TG_POOL_ALLOC(b->s, &b->visited, words * 8);
+    TG_HIP_CHECK(hipMemsetAsync(b->visited, 0, words * 8, b->s->stream));
+    return TG_OK;
+}
+
 __global__ void k_bitmap_concat(const uint64_t* __restrict__ src, int64_t n,
                                 int64_t at, uint64_t* __restrict__ dst)
 {
@@ -1151,15 +1261,30 @@ struct LookupJoinOp : tg_operator {
     std::vector<int32_t> key_channels;
     std::vector<tg_type> probe_types;
     std::vector<int32_t> probe_output;
-    bool outer = false;             /* probe-outer (LEFT) */
+    bool outer = false;             /* probe-outer (LEFT, FULL) */
+    bool record = false;            /* build-outer (RIGHT, FULL): mark visited */
+    bool counted = false;           /* still in bridge->recording */
+
+    void release_recording()
+    {
+        if (counted) { bridge->recording--; counted = false; }
+    }
+
+    tg_status finish() override
+    {
+        release_recording();
+        input_finished = true;
+        return TG_OK;
+    }
 
     tg_status add_input(const tg_page* page) override
     {
         if (!bridge->built) { TG_SET_ERR("lookup source not built (finish the builder first)"); return TG_ERR_STATE; }
-        if (bridge->t.set_bitmap && !bridge->t.csr) { TG_SET_ERR("set-builder bridge supports semi join only"); return TG_ERR_UNSUPPORTED; }
+        if (bridge_is_set_only(bridge)) { TG_SET_ERR("set-builder bridge supports semi join only"); return TG_ERR_UNSUPPORTED; }
         tg_status st = check_probe_keys(bridge, page, key_channels.data(),
                                         key_channels.size());
         if (st != TG_OK) return st;
+        if (!record) bridge->plain_probed = true;
         DevPage in;
         st = tg_upload_page(s, page, &in);
         if (st != TG_OK) return st;
@@ -1299,6 +1424,18 @@ struct LookupJoinOp : tg_operator {
             TG_HIP_CHECK(hipStreamSynchronize(s->stream));
         }
 
+        /* build-outer: whichever path ran, d_ob[0..total) is the matched
+         * build row list — record it (stream-ordered before the gathers) */
+        if (record) {
+            st = bridge_ensure_visited(bridge);
+            if (st != TG_OK) return st;
+            if (total > 0) {
+                hipLaunchKernelGGL(k_mark_visited, dim3(tg_grid_for(total)), dim3(TG_BLOCK),
+                                   0, s->stream, d_ob, total, bridge->visited);
+                TG_HIP_CHECK(hipGetLastError());
+            }
+        }
+
         /* output: probe output channels gathered by probe row, then build
          * output channels gathered by build row (LookupJoinPageBuilder) */
         DevPage outp;
@@ -1336,6 +1473,127 @@ struct LookupJoinOp : tg_operator {
 
     ~LookupJoinOp() override
     {
+        release_recording();     /* closed unfinished: the bridge outlives us */
+        for (auto& p : out_pages_) tg_free_page(s, &p);
+    }
+};
+
+/* ---- lookup-outer operator (LookupOuterOperator.java): a source operator
+ * that emits, once every recording probe operator on the bridge has
+ * finished, one row per build row no probe row matched — the probe output
+ * channels all NULL, then the build output channels gathered from the build
+ * row; ascending global build row order, one page ---- */
+struct LookupOuterOp : tg_operator {
+    tg_join_bridge* bridge = nullptr;
+    std::vector<tg_type> probe_out_types;
+    bool emitted = false;
+
+    int needs_input() override { return 0; }
+
+    tg_status add_input(const tg_page*) override
+    {
+        TG_SET_ERR("the lookup-outer operator is a source: it takes no input");
+        return TG_ERR_STATE;
+    }
+
+    /* an all-NULL column: cleared validity bits, zeroed data, VARCHAR cells
+     * of zero length (the LEFT join's build-side convention) */
+    tg_status null_column(tg_type type, int64_t count, DevBlock* b)
+    {
+        b->type = type;
+        b->n = count;
+        int64_t words = (count + 63) / 64;
+        TG_POOL_ALLOC(s, &b->valid, words * 8);
+        TG_HIP_CHECK(hipMemsetAsync(b->valid, 0, words * 8, s->stream));
+        if (type == TG_VARCHAR) {
+            TG_POOL_ALLOC(s, &b->offsets, (count + 1) * 4);
+            TG_HIP_CHECK(hipMemsetAsync(b->offsets, 0, (count + 1) * 4, s->stream));
+            TG_POOL_ALLOC(s, &b->data, 1);
+            return TG_OK;
+        }
+        TG_POOL_ALLOC(s, &b->data, count * b->elem_size());
+        TG_HIP_CHECK(hipMemsetAsync(b->data, 0, count * b->elem_size(), s->stream));
+        return TG_OK;
+    }
+
+    tg_status emit_unmatched()
+    {
+        const int64_t n = bridge->t.n;
+        if (n == 0) return TG_OK;
+        /* no recording operator ever added a page: every row is unvisited */
+        tg_status st = bridge_ensure_visited(bridge);
+        if (st != TG_OK) return st;
+        int64_t words = (n + 63) / 64;
+        int32_t* d_counts = nullptr;
+        int64_t* d_offsets = nullptr;
+        int64_t* d_total = nullptr;
+        TG_POOL_ALLOC(s, &d_counts, words * 4);
+        TG_POOL_ALLOC(s, &d_offsets, words * 8);
+        TG_POOL_ALLOC(s, &d_total, 8);
+        hipLaunchKernelGGL(k_unvisited_count, dim3(tg_grid_for(words)), dim3(TG_BLOCK),
+                           0, s->stream, bridge->visited, n, d_counts);
+        TG_HIP_CHECK(hipGetLastError());
+        st = run_scan_counts(s, d_counts, words, d_offsets, d_total);
+        if (st != TG_OK) return st;
+        int64_t total = 0;
+        TG_HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s->stream));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        if (total > 0) {
+            int32_t* d_rows = nullptr;
+            TG_POOL_ALLOC(s, &d_rows, total * 4);
+            hipLaunchKernelGGL(k_unvisited_rows, dim3(tg_grid_for(words)), dim3(TG_BLOCK),
+                               0, s->stream, bridge->visited, n, d_offsets, d_rows);
+            TG_HIP_CHECK(hipGetLastError());
+            DevPage outp;
+            outp.n = total;
+            for (tg_type ty : probe_out_types) {
+                DevBlock ob;
+                st = null_column(ty, total, &ob);
+                if (st != TG_OK) return st;
+                outp.blocks.push_back(ob);
+            }
+            for (int32_t ch : bridge->build_output_channels) {
+                DevBlock ob;
+                st = run_gather(s, bridge->build_channels[ch], d_rows, (int32_t)total, &ob);
+                if (st != TG_OK) return st;
+                outp.blocks.push_back(ob);
+            }
+            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+            tg_pool_free(s, d_rows);
+            stage_output(std::move(outp));
+        }
+        tg_pool_free(s, d_counts);
+        tg_pool_free(s, d_offsets);
+        tg_pool_free(s, d_total);
+        return TG_OK;
+    }
+
+    tg_status get_output(tg_page* out, int* finished) override
+    {
+        if (!emitted) {
+            /* all state rules are checked here, on the host, before a launch */
+            if (!bridge->built) { TG_SET_ERR("lookup source not built (finish the builder first)"); return TG_ERR_STATE; }
+            if (bridge_is_set_only(bridge)) { TG_SET_ERR("set-builder bridge supports semi join only"); return TG_ERR_UNSUPPORTED; }
+            if (bridge->recording > 0) {
+                TG_SET_ERR("%d recording lookup join operator(s) on this bridge have not finished",
+                           bridge->recording);
+                return TG_ERR_STATE;
+            }
+            if (bridge->plain_probed) {
+                TG_SET_ERR("a join_type 0 or 1 lookup join probed this bridge: its matches were not recorded");
+                return TG_ERR_STATE;
+            }
+            tg_status st = emit_unmatched();
+            if (st != TG_OK) return st;
+            emitted = true;
+            input_finished = true;
+        }
+        emit_staged(out, finished);
+        return TG_OK;
+    }
+
+    ~LookupOuterOp() override
+    {
         for (auto& p : out_pages_) tg_free_page(s, &p);
     }
 };
@@ -1362,6 +1620,7 @@ extern "C" void tg_join_bridge_close(tg_join_bridge* b)
     if (b->t.kv) tg_pool_free(b->s, (void*)b->t.kv);
     if (b->t.set_bitmap) tg_pool_free(b->s, (void*)b->t.set_bitmap);
     if (b->d_bkeys) tg_pool_free(b->s, b->d_bkeys);
+    if (b->visited) tg_pool_free(b->s, b->visited);
     for (auto& c : b->build_channels) {
         if (c.data) tg_pool_free(b->s, c.data);
         if (c.valid) tg_pool_free(b->s, c.valid);
@@ -1561,7 +1820,8 @@ extern "C" tg_status tg_lookup_join_create_ex(tg_session* s, tg_join_bridge* bri
     const int32_t* probe_types, int32_t n_probe_channels,
     const int32_t* key_channels, int32_t n_key_channels,
     const int32_t* probe_output_channels, int32_t n_probe_output,
-    int32_t join_type /* 0 inner, 1 probe-outer */, tg_operator** out);
+    int32_t join_type /* 0 inner, 1 probe-outer, 2 build-outer, 3 full */,
+    tg_operator** out);
 
 extern "C" tg_status tg_lookup_join_create(tg_session* s, tg_join_bridge* bridge,
     const int32_t* probe_types, int32_t n_probe_channels,
@@ -1590,11 +1850,44 @@ extern "C" tg_status tg_lookup_join_create_ex(tg_session* s, tg_join_bridge* bri
     const int32_t* probe_output_channels, int32_t n_probe_output,
     int32_t join_type, tg_operator** out)
 {
+    if (join_type < 0 || join_type > 3) {
+        TG_SET_ERR("join_type %d: 0 inner, 1 probe-outer, 2 build-outer, 3 full", join_type);
+        return TG_ERR_INVALID_ARG;
+    }
     tg_status st = tg_lookup_join_create(s, bridge, probe_types, n_probe_channels,
                                          key_channels, n_key_channels,
                                          probe_output_channels, n_probe_output, out);
     if (st != TG_OK) return st;
-    static_cast<LookupJoinOp*>(*out)->outer = (join_type == 1);
+    auto* op = static_cast<LookupJoinOp*>(*out);
+    op->outer = (join_type == 1 || join_type == 3);
+    if (join_type >= 2) {    /* build-outer: counted until finished or closed */
+        op->record = true;
+        op->counted = true;
+        bridge->recording++;
+    }
+    return TG_OK;
+}
+
+extern "C" tg_status tg_lookup_outer_create(tg_session* s, tg_join_bridge* bridge,
+    const int32_t* probe_output_types, int32_t n_probe_output, tg_operator** out)
+{
+    if (!s || !bridge || !out || n_probe_output < 0 ||
+        (n_probe_output > 0 && !probe_output_types)) {
+        TG_SET_ERR("null arg");
+        return TG_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n_probe_output; i++) {
+        if (probe_output_types[i] < TG_BIGINT || probe_output_types[i] > TG_VARCHAR) {
+            TG_SET_ERR("probe output type %d at position %d", probe_output_types[i], i);
+            return TG_ERR_INVALID_ARG;
+        }
+    }
+    auto* op = new LookupOuterOp();
+    op->s = s;
+    op->bridge = bridge;
+    for (int i = 0; i < n_probe_output; i++)
+        op->probe_out_types.push_back((tg_type)probe_output_types[i]);
+    *out = op;
     return TG_OK;
 }
 

@@ -338,7 +338,12 @@ def hash_builder(session, bridge, build_types, key_channels, output_channels):
 
 def lookup_join(session, bridge, probe_types, key_channels, probe_output_channels,
                 join_type=0):
-    """join_type: 0 inner, 1 probe-outer (LEFT)."""
+    """join_type: 0 inner, 1 probe-outer (LEFT), 2 build-outer (RIGHT),
+    3 FULL. 2 and 3 emit what 0 and 1 emit and record the matched build rows
+    on the bridge; once every such operator is finished (or closed),
+    lookup_outer(session, bridge, ...) emits the build rows nobody matched.
+    Close the operator before the bridge. Other values raise
+    (TG_ERR_INVALID_ARG)."""
     h = ctypes.c_void_p()
     pt = _i32arr(probe_types)
     kc = _i32arr(key_channels)
@@ -348,6 +353,27 @@ def lookup_join(session, bridge, probe_types, key_channels, probe_output_channel
                                          len(oc), join_type, ctypes.byref(h)))
     op = Operator(session, h)
     op._keep = (pt, kc, oc)
+    return op
+
+
+_lib.tg_lookup_outer_create.restype = ctypes.c_int
+_lib.tg_lookup_outer_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_void_p]
+
+
+def lookup_outer(session, bridge, probe_output_types):
+    """LookupOuterOperator analog, the source operator that completes a RIGHT
+    or FULL join: drain() gives at most one page holding, in ascending build
+    row order, every build row no recording lookup join matched — first one
+    all-NULL column per entry of probe_output_types, then the bridge's build
+    output channels."""
+    h = ctypes.c_void_p()
+    pt = _i32arr(probe_output_types)
+    _check(_lib.tg_lookup_outer_create(session._h, bridge._h, pt.ctypes.data,
+                                       len(pt), ctypes.byref(h)))
+    op = Operator(session, h)
+    op._keep = (pt,)
     return op
 
 
