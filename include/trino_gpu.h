@@ -369,11 +369,30 @@ tg_status tg_tpch_gen_orders3(tg_session*, double scale_factor,
     int64_t* d_cmnt_off, int32_t* d_cmnt_len);
 /* 300 MiB dbgen text pool, device-resident (built host-side, cached) */
 tg_status tg_tpch_pool(tg_session*, const uint8_t** d_pool);
-/* LIKE '%a%b%' (no '_') over pool slices / var-width columns -> 0/1 flags */
+/* LIKE over pool slices / var-width columns -> d_flags[i] = 0 or 1
+ * (LikeFunctions semantics, '%' the only wildcard, bytes not characters, no
+ * escape). Forms: 'abc' exact (text == "abc"); 'abc%' prefix; '%abc' suffix;
+ * '%abc%' floating; 'a%b%c' pins the first segment to the start and the last
+ * to the end, the segments between are found leftmost and never overlap
+ * ('ab%ab' needs four bytes). '' matches only the empty text; '%' and '%%'
+ * match every text. Limits: at most 4 literal segments and 63 pattern bytes;
+ * any '_' is rejected; all three are TG_ERR_UNSUPPORTED. A null session,
+ * pointer or pattern, or n < 0, is TG_ERR_INVALID_ARG. Every rejection
+ * happens before anything is launched, so d_flags is untouched; n == 0
+ * returns TG_OK and writes nothing. The flags carry no NULL: a NULL row's
+ * flag is whatever its bytes give, and the caller masks it with the
+ * column's validity. tg_pool_like_flags picks its path by TG_LIKE_IDX, read
+ * on every call (0 byte scan, 1 occurrence index for floating patterns,
+ * 2 offset-sorted scan; unset: 2 from 2^20 rows, else 0). */
 tg_status tg_pool_like_flags(tg_session*, const int64_t* d_offs,
     const int32_t* d_lens, int64_t n, const char* pattern, uint8_t* d_flags);
 tg_status tg_varchar_like_flags(tg_session*, const uint8_t* d_bytes,
     const int32_t* d_offsets, int64_t n, const char* pattern, uint8_t* d_flags);
+/* host-only hook for tests and host drivers (no session, no GPU): *out =
+ * (bytes[0, len) LIKE pattern) through the same matcher the kernels run
+ * (csrc/like_match.h). Same rejections as above; len == 0 may pass NULL. */
+tg_status tg_like_match_host(const char* pattern, const uint8_t* bytes,
+    int32_t len, int32_t* out);
 /* s_comment var-width column incl. the BBB "Customer ...Complaints/
  * Recommends" overlay (10 rows per 10,000 suppliers) */
 tg_status tg_tpch_gen_supplier_comments(tg_session*, double scale_factor,
@@ -455,7 +474,14 @@ tg_status tg_pa_controller_on_flush(tg_pa_controller*, int64_t bytes,
 tg_status tg_hash_aggregation_set_controller(tg_operator*, tg_pa_controller*);
 
 /* MarkDistinctOperator analog: appends a BOOLEAN channel marking each
- * row's first occurrence over the key channels (streaming pass-through) */
+ * row's first occurrence over the key channels (streaming pass-through:
+ * every add_input stages its page, input channels unchanged with their
+ * validity, then the flag channel, which has no bitmap). 0..7 key channels
+ * of any type. NULL is a key value in every position ((NULL,1), (NULL,2),
+ * (NULL,NULL) are three keys), every NaN is one key, -0.0 is 0.0, VARCHAR
+ * compares by bytes and '' is not NULL. Zero key channels: only the first
+ * row of the whole input is flagged. Zero-row pages are accepted anywhere,
+ * VARCHAR keys included, and come out as zero-row pages. */
 tg_status tg_mark_distinct_create(tg_session*, const int32_t* key_channels,
     int32_t n_key_channels, const int32_t* key_types, tg_operator**);
 
@@ -474,7 +500,13 @@ tg_status tg_dense_aggregation_create(tg_session*, int32_t key_channel,
 /* sort-based DISTINCT of a non-negative BIGINT device column (radix sort +
  * unique compaction; `bits` = key width to sort). For near-all-unique
  * dedups (count(DISTINCT ...)) where hash aggregation pays random keystore
- * probes per row. d_out sized n; *out_n gets the distinct count. */
+ * probes per row. d_out sized n; *out_n gets the distinct count and d_out
+ * the distinct keys ascending. Every key must lie in [0, 2^bits) (bits = 64:
+ * [0, 2^63)); nothing checks it, a check would cost a pass over the
+ * column. Only the low `bits` bits order the sort, so with a wider key the
+ * output may be unsorted and may repeat a key, but it loses and invents
+ * none. n = 0 gives 0. A null pointer, n < 0 or bits outside 1..64 is
+ * TG_ERR_INVALID_ARG before anything is launched. */
 tg_status tg_dedup_i64(tg_session*, const int64_t* d_in, int64_t n,
     int32_t bits, int64_t* d_out, int64_t* out_n);
 

@@ -72,3 +72,67 @@ def test_partial_agg_controller_state_machine():
     assert not c2.disabled
     c.close()
     c2.close()
+
+
+def test_like_matcher_exhaustive_on_host():
+    """The whole LIKE matcher (csrc/like_match.h: parse_like, like_find_byte,
+    like_match, the code the kernels run) through tg_like_match_host against
+    the plain-Python ref_like of the GPU matrix: 364 patterns x 427 texts =
+    155,428 pairs, each text at all 8 start alignments. No GPU."""
+    _built()
+    import numpy as np
+    from test_gpu_text_distinct_matrix import like_exhaustive_set, ref_like
+    lib = ctypes.CDLL(SO)
+    fn = lib.tg_like_match_host
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int32,
+                   ctypes.POINTER(ctypes.c_int32)]
+    pats, texts = like_exhaustive_set()
+    assert len(pats) == 364 and len(texts) == 427
+    # one arena; text t at alignment a starts at an address = a (mod 8)
+    arena = np.zeros(sum(len(t) + 16 for t in texts) * 8 + 64, np.uint8)
+    base = arena.ctypes.data
+    at = (-base) % 8
+    where = []
+    for t in texts:
+        for a in range(8):
+            while (base + at) % 8 != a:
+                at += 1
+            arena[at:at + len(t)] = np.frombuffer(t, np.uint8)
+            where.append((base + at, len(t), t))
+            at += len(t) + 1
+    out = ctypes.c_int32(-1)
+    ref = ctypes.byref(out)
+    wrong = []
+    for p in pats:
+        verdict = {}
+        for addr, n, t in where:
+            if t not in verdict:
+                verdict[t] = ref_like(p, t)
+            assert fn(p, addr, n, ref) == 0
+            if out.value != verdict[t]:
+                wrong.append((p, t, addr % 8, out.value))
+    bad_pats = sorted({w[0] for w in wrong})
+    assert not wrong, (len(wrong), len(bad_pats), bad_pats[:10], wrong[:5])
+
+
+def test_like_match_host_rejections():
+    _built()
+    lib = ctypes.CDLL(SO)
+    fn = lib.tg_like_match_host
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32,
+                   ctypes.POINTER(ctypes.c_int32)]
+    out = ctypes.c_int32(-1)
+    ref = ctypes.byref(out)
+    assert fn(b"", None, 0, ref) == 0 and out.value == 1      # '' LIKE ''
+    assert fn(b"%", None, 0, ref) == 0 and out.value == 1
+    assert fn(b"a", None, 0, ref) == 0 and out.value == 0
+    out.value = -1
+    for args in ((None, b"a", 1, ref), (b"a", None, 1, ref), (b"a", b"a", -1, ref),
+                 (b"a", b"a", 1, None)):
+        assert fn(*args) == 1                                  # TG_ERR_INVALID_ARG
+    for p in (b"a_", b"a%b%c%d%e", b"a" * 64):
+        assert fn(p, b"a", 1, ref) == 6                        # TG_ERR_UNSUPPORTED
+    assert fn(b"a%b%c%d", b"abcd", 4, ref) == 0 and out.value == 1
+    assert fn(b"a" * 63, b"a" * 63, 63, ref) == 0 and out.value == 1

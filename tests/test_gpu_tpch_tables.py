@@ -217,11 +217,10 @@ class TestMinMaxAgg:
 
 
 class TestIndexedPoolLike:
-    def test_indexed_vs_byte_scan(self, sess, ops):
+    def test_indexed_vs_byte_scan(self, sess, ops, monkeypatch):
         """The indexed pool LIKE (segment-occurrence index over the 300 MiB
         pool + per-row binary searches) must agree bitwise with the per-row
         byte-scan kernel on the same slices (TG_LIKE_IDX forces each path)."""
-        import os
         from trino_amd import _lib, _check
         no = int(1_500_000 * SF)
         bo = [None, None, None, None, None, None,
@@ -231,11 +230,10 @@ class TestIndexedPoolLike:
             outs = []
             for mode in ("0", "1", "2"):    # byte scan / index / sorted scan
                 d = dbuf(sess, no)
-                os.environ["TG_LIKE_IDX"] = mode
+                monkeypatch.setenv("TG_LIKE_IDX", mode)
                 ops.pool_like_flags(sess, bo[6], bo[7], no, pat, d)
                 outs.append(dl(sess, np.empty(no, np.uint8), d))
                 dfree(sess, d)
-            del os.environ["TG_LIKE_IDX"]
             assert np.array_equal(outs[0], outs[1]), pat
             assert np.array_equal(outs[0], outs[2]), pat
             assert outs[0].sum() > 0              # pattern actually matches

@@ -7,6 +7,8 @@ ArrayPositionLinks.java:24-45 chain semantics, HashGenerator.java:41-46 and
 LocalPartitionGenerator.java:76-80 partition reduction). Python reimplements
 each formula independently to cross-check the C restatement.
 """
+import math
+
 import numpy as np
 import pytest
 
@@ -821,3 +823,218 @@ class TestOrderingMatrixHost:
         assert sorted(i for p in parts for i in p) == list(range(500))
         assert all(p == sorted(p) for p in parts)
         assert all(pids[i] == q for q, p in enumerate(parts) for i in p)
+
+
+class TestTextDistinctMatrixHost:
+    """Host-side checks for tests/test_gpu_text_distinct_matrix.py: the
+    references give hand-written verdicts (ref_like also agrees with
+    re.fullmatch on the exhaustive set), every LIKE case expects both
+    verdicts, the constants the shapes rest on equal the ones parsed from the
+    sources, and each shape reaches the path it names. No GPU."""
+
+    @staticmethod
+    def mx():
+        import test_gpu_text_distinct_matrix as m
+        return m
+
+    def test_ref_like_equals_re_fullmatch(self):
+        import re
+        m = self.mx()
+        pats, texts = m.like_exhaustive_set()
+        assert len(pats) == 364 and len(texts) == 427
+        for p in pats:
+            rx = re.compile(b".*".join(re.escape(s) for s in p.split(b"%")), re.S)
+            for t in texts:
+                assert m.ref_like(p, t) == (1 if rx.fullmatch(t) else 0), (p, t)
+
+    def test_ref_like_by_hand(self):
+        m = self.mx()
+        for p, t, v in m.ANCHOR_BY_HAND + (
+                (b"abc", b"abcd", 0), (b"abc", b"abc", 1), (b"abc", b"xabc", 0),   # L1
+                (b"", b"", 1), (b"", b"a", 0), (b"%", b"a", 1), (b"%%", b"", 1),   # L2
+                (b"a%b%c", b"abc", 1), (b"a%b%c", b"acb", 0), (b"a%c", b"ac", 1),
+                (b"%\xc3\xa9%", b"a\xc3\xa9", 1), (b"%\xc3\xa9%", b"\xc3a\xa9", 0),
+                (b"%a%", b"\x00a\x00", 1)):
+            assert m.ref_like(p, t) == v, (p, t)
+
+    def test_constants_follow_the_sources(self):
+        m = self.mx()
+        k = m.source_constants()
+        assert (k["LIKE_MAX_SEGS"], k["LIKE_MAX_PAT"]) == (4, 64) == \
+            (m.LIKE_MAX_SEGS, m.LIKE_MAX_PAT)
+        assert (k["TG_BLOCK"], k["TG_MAX_BLOCKS"]) == (256, 2048)
+        assert k["TG_BLOCK"] * k["TG_MAX_BLOCKS"] == m.GRID_THREADS
+        assert m.GRID_N == m.GRID_THREADS + 257 == 524_545
+        assert 1 << k["SORTED_SWITCH_SHIFT"] == m.SORTED_SWITCH == 1 << 20
+        assert len(m.pool_bytes()) <= 1 << k["SORTED_KEY_BITS"]   # offsets fit the sort
+        assert 1 << k["INIT_GROUPS_SHIFT"] == m.INIT_GROUPS == 1 << 16
+        assert 1 << k["INIT_CAP_SHIFT"] == m.INIT_CAP == 1 << 17
+        assert k["LOAD_FACTOR"] == m.LOAD_FACTOR == 0.7
+        # the limits cases sit on the limits
+        acc = m.like_case("limits_accepted")[1]
+        assert max(p.count(b"%") + 1 for p in acc if not p.startswith(b"%")) == \
+            m.LIKE_MAX_SEGS
+        assert max(len(p) for p in acc) == m.LIKE_MAX_PAT - 1
+        rej = m.LIKE_REJECTED
+        assert any(len(p) == m.LIKE_MAX_PAT and b"_" not in p and b"%" not in p
+                   for p in rej)
+        assert any(len([s for s in p.split(b"%") if s]) == m.LIKE_MAX_SEGS + 1
+                   and b"_" not in p for p in rej)
+        assert all(b"_" in p or len(p) >= m.LIKE_MAX_PAT or
+                   len([s for s in p.split(b"%") if s]) > m.LIKE_MAX_SEGS
+                   for p in rej)
+
+    def test_every_varchar_like_case_has_both_verdicts(self):
+        m = self.mx()
+        names = [c[0] for c in m.varchar_like_cases()]
+        assert names == ["no_percent", "empty_pattern", "anchor_matrix",
+                         "swar_lanes", "bytes_not_chars", "limits_accepted",
+                         "grid_stride"]
+        for name, patterns, rows in m.varchar_like_cases():
+            for p in patterns:
+                exp = [m.ref_like(p, t) for t in rows]
+                if p in m.LIKE_ALL_ONE:
+                    assert all(exp), (name, p)
+                else:
+                    assert 0 < sum(exp) < len(exp), (name, p)
+        anchor_rows = m.like_case("anchor_matrix")[2]
+        assert all(t in anchor_rows for _, t, _ in m.ANCHOR_BY_HAND)
+        assert set(m.all_strings(b"abc", 5)) <= set(anchor_rows)
+        assert set(m.ANCHOR_PATTERNS) >= {
+            b"abc", b"abc%", b"%abc", b"%abc%", b"a%c", b"a%b%c", b"%a%b",
+            b"a%b%", b"ab%ab", b"%", b"%%", b"%%a%%"}
+
+    def test_swar_rows_cover_every_alignment_and_position(self):
+        m = self.mx()
+        texts = m.swar_texts()
+        rows = m.rows_at_every_alignment(texts)
+        seen, at = {}, 0
+        for t in rows:
+            seen.setdefault(t, set()).add(at % 8)
+            at += len(t)
+        for t in texts:
+            assert seen[t] == set(range(8)), t
+        for L in range(2, 41):
+            for pos in range(L - 1):               # pos == L - 2: the last legal start
+                for near in m.SWAR_NEAR:
+                    hits = [t for t in texts if len(t) == L and
+                            t.find(m.SWAR_SEG) == pos and
+                            (near is None or pos == 0 or t.startswith(near[:1]))]
+                    assert hits, (L, pos, near)
+        near = {bytes([ord("Q") ^ 1]), bytes([ord("Q") ^ 0x80]), b"\x00", b"\xff", b"Qy"}
+        assert near == {x for x in m.SWAR_NEAR if x}
+        rows = m.like_case("grid_stride")[2]
+        assert len(rows) == m.GRID_N and max(map(len, rows)) == 12
+        assert rows[0] == rows[-1] == rows[m.GRID_THREADS] == b""
+
+    def test_pool_cases(self):
+        m = self.mx()
+        pool = m.pool_bytes()
+        P = len(pool)
+        assert P == 300 * 1024 * 1024
+        for offs, lens in (m.pool_constructed_slices(), m.pool_switch_slices()):
+            assert offs.dtype == np.int64 and lens.dtype == np.int32
+            assert offs.min() >= 0 and lens.min() >= 0
+            assert int((offs + lens).max()) <= P
+        offs, lens = m.pool_constructed_slices()
+        assert int((offs + lens).max()) == P and int(offs.min()) == 0
+        assert (lens == 0).any()
+        assert len(offs) >= m.N_POOL_RANDOM
+        assert pool.find(m.POOL_NOWHERE.strip(b"%")) == -1
+        for p in m.POOL_PATTERNS:
+            exp = m.pool_constructed_expected(p)
+            if p == m.POOL_NOWHERE:
+                assert not exp.any()
+            else:
+                assert m.both_verdicts(exp), p
+        # the hand-built slices do what their comments say
+        w = m.POOL_WORDS[0]
+        o = m.occurrences(pool, w, 1, start=64)[0]
+        sl = list(zip(offs.tolist(), lens.tolist()))
+        i = sl.index((o - 10, 10 + len(w)))
+        assert m.ref_like(b"%" + w, pool[o - 10:o + len(w)]) == 1
+        assert m.ref_like(b"%" + w + b"%", pool[o - 10:o + len(w) - 1]) == 0
+        assert sl[i + 1] == (o - 10, 10 + len(w) - 1)
+        assert sl[i + 4] == (o, len(w)) and m.ref_like(w, pool[o:o + len(w)]) == 1
+        # anchored, exact and '' patterns cannot take the index in mode 1
+        assert set(m.POOL_FLOATING) | {m.POOL_NOWHERE} == {
+            p for p in m.POOL_PATTERNS if p[:1] == b"%" and p[-1:] == b"%"
+            and p.strip(b"%")}
+        # default switch: duplicates of one offset with different verdicts
+        offs, lens = m.pool_switch_slices()
+        assert len(offs) == m.SORTED_SWITCH
+        exp = m.pool_switch_expected()
+        assert m.both_verdicts(exp) and m.both_verdicts(exp[:-1])
+        by_off = {}
+        for o_, l_, e_ in zip(offs.tolist(), lens.tolist(), exp.tolist()):
+            by_off.setdefault(o_, set()).add((l_, e_))
+        mixed = [v for v in by_off.values()
+                 if {e for _, e in v} == {0, 1} and len({l for l, _ in v}) >= 4]
+        assert len(mixed) >= 50
+
+    def test_ref_mark_distinct_by_hand(self):
+        m = self.mx()
+        nan2 = float.fromhex("nan")
+        rows = [(None, 1), (None, 2), (None, None), (None, 1), (1, None),
+                (None, None)]
+        assert m.ref_mark_distinct(rows) == [1, 1, 1, 0, 1, 0]
+        rows = [(0.0,), (-0.0,), (math.nan,), (nan2,), (-math.nan,), (math.inf,),
+                (-math.inf,), (None,), (math.inf,)]
+        assert m.ref_mark_distinct(rows) == [1, 0, 1, 0, 0, 1, 1, 1, 0]
+        rows = [(b"",), (None,), (b"a",), (b"ab",), (b"ac",), (b"",), (b"ab",),
+                (b"\x00",)]
+        assert m.ref_mark_distinct(rows) == [1, 1, 1, 1, 1, 0, 0, 1]
+        assert m.ref_mark_distinct([(), (), ()]) == [1, 0, 0]
+        # the double key column really holds the named values
+        v = m.double_key_values(64, 1)
+        bits = v.view(np.uint64).tolist()
+        assert set(m.NAN_PAYLOADS) <= set(bits) and any(b >> 63 for b in m.NAN_PAYLOADS)
+        assert 0 in bits and 1 << 63 in bits                       # 0.0 and -0.0
+        assert math.inf in v.tolist() and -math.inf in v.tolist()
+        s = m.varchar_key_values(64, 1)
+        assert b"" in s and b"abc" in s and b"abd" in s and b"ab" in s
+
+    def test_ref_partial_state_by_hand(self):
+        m = self.mx()
+        f = m.ref_partial_state
+        one = m.f64_bits(1.0)
+        assert f(m.FN_COUNT_STAR, None) == (1,) and f(m.FN_COUNT_STAR, 5) == (1,)
+        assert f(m.FN_COUNT_COL, None) == (0,) and f(m.FN_COUNT_COL, -5) == (1,)
+        assert f(m.FN_SUM_I64, None) == (0,) and f(m.FN_SUM_I64, -5) == (-5,)
+        assert f(m.FN_SUM_F64, None) == (0,) and f(m.FN_SUM_F64, 1.0) == (one,)
+        assert f(m.FN_MIN_I64, None) == (2 ** 63 - 1,) and f(m.FN_MIN_I64, 7) == (7,)
+        assert f(m.FN_MAX_I64, None) == (-2 ** 63,) and f(m.FN_MAX_I64, 7) == (7,)
+        assert f(m.FN_AVG_F64, None) == (0, 0) and f(m.FN_AVG_F64, 1.0) == (1, one)
+        assert f(m.FN_SUM_F64_EXACT, None, 10) == (0, 0)
+        assert f(m.FN_SUM_F64_EXACT, 1.5, 10) == (1536, 0)
+        assert f(m.FN_SUM_F64_EXACT, -1.5, 10) == (-1536, -1)      # two's complement
+        assert f(m.FN_SUM_F64_EXACT, 2.0 ** -10, 10) == (1, 0)
+
+    def test_growth_and_page_shapes(self):
+        m = self.mx()
+        pages = m.mark_growth_pages()
+        assert len(pages) == 3
+        seen, before = set(), []
+        for p in pages:
+            keys = p[0].values.tolist()
+            before.append((len(seen), len(keys)))
+            seen |= set(keys)
+        assert [b for b, _ in before] == [0, m.GROWTH_NEW, 2 * m.GROWTH_NEW]
+        (g1, n1), (g2, n2), (g3, n3) = before
+        cap07 = int(m.INIT_CAP * m.LOAD_FACTOR)
+        assert g1 + n1 <= m.INIT_GROUPS and g1 + n1 <= cap07       # page 1: no growth
+        assert g2 + n2 > m.INIT_GROUPS and g2 + n2 <= cap07        # page 2: key store
+        assert g3 + n3 > cap07 and g3 + n3 <= 2 * m.INIT_GROUPS    # page 3: slot table
+        assert set(pages[1][0].values.tolist()) & set(pages[0][0].values.tolist())
+        assert m.PA_BITMAP_NS == (63, 64, 65, 129)
+        assert len(m.mark_multi_case(7)[0]) == 8                    # 7 keys + 1 value
+        # dedup: keys fit their width, the ends are present
+        for name, keys, bits in m.dedup_cases():
+            if len(keys):
+                assert 0 <= int(keys.min()) and int(keys.max()) < 2 ** min(bits, 63), name
+        ends = {b: k for n_, k, b in m.dedup_cases() if n_.startswith("ends_")}
+        assert sorted(ends) == [1, 8, 31, 32, 33, 52, 64]
+        for b, k in ends.items():
+            assert set(k.tolist()) == {0, 2 ** min(b, 63) - 1}
+        sizes = {len(k) for _, k, _ in m.dedup_cases()}
+        assert {0, 1, 2, m.GRID_N, (1 << 20) + 3} <= sizes

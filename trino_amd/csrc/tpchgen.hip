@@ -572,70 +572,10 @@ extern "C" tg_status tg_tpch_pool(tg_session* s, const uint8_t** d_pool)
 }
 
 /* LIKE '%seg1%seg2%...%' over pool slices: per row, find each literal
- * segment in order within pool[off, off+len). anchor_start/end pin the
- * first/last segment (LIKE without leading/trailing %%).
- * Mirrors io.trino.type.LikeFunctions / LikePattern matching semantics for
- * patterns without '_' wildcards. */
-#define LIKE_MAX_SEGS 4
-#define LIKE_MAX_PAT 64
-struct LikePat {
-    char bytes[LIKE_MAX_PAT];
-    int seg_off[LIKE_MAX_SEGS], seg_len[LIKE_MAX_SEGS];
-    int n_segs, anchor_start, anchor_end;
-};
-
-/* SWAR first-byte scan: next index >= from with s[i] == c, else -1
- * (byte-loop scanning measured 38.8 ms for Q13's 150M x ~49 B comments) */
-__device__ static inline int like_find_byte(const uint8_t* s, int from,
-                                            int len, uint8_t c)
-{
-    int i = from;
-    for (; i < len && ((uintptr_t)(s + i) & 7); i++)
-        if (s[i] == c) return i;
-    const uint64_t pat = 0x0101010101010101ull * c;
-    for (; i + 8 <= len; i += 8) {
-        uint64_t w = *(const uint64_t*)(s + i) ^ pat;
-        uint64_t m = (w - 0x0101010101010101ull) & ~w & 0x8080808080808080ull;
-        if (m) return i + (__ffsll((unsigned long long)m) - 1) / 8;
-    }
-    for (; i < len; i++)
-        if (s[i] == c) return i;
-    return -1;
-}
-
-__device__ static bool like_match(const uint8_t* txt, int len, const LikePat& p)
-{
-    int pos = 0;
-    for (int k = 0; k < p.n_segs; k++) {
-        int sl = p.seg_len[k];
-        const char* seg = p.bytes + p.seg_off[k];
-        if (k == 0 && p.anchor_start) {
-            if (len < sl) return false;
-            for (int i = 0; i < sl; i++) if (txt[i] != (uint8_t)seg[i]) return false;
-            pos = sl;
-            continue;
-        }
-        if (k == p.n_segs - 1 && p.anchor_end) {
-            if (len - pos < sl) return false;
-            for (int i = 0; i < sl; i++)
-                if (txt[len - sl + i] != (uint8_t)seg[i]) return false;
-            pos = len;
-            continue;
-        }
-        bool found = false;
-        int i = pos;
-        while (i + sl <= len) {
-            i = like_find_byte(txt, i, len - sl + 1, (uint8_t)seg[0]);
-            if (i < 0) break;
-            bool eq = true;
-            for (int j = 1; j < sl && eq; j++) eq = txt[i + j] == (uint8_t)seg[j];
-            if (eq) { pos = i + sl; found = true; break; }
-            i++;
-        }
-        if (!found) return false;
-    }
-    return true;
-}
+ * segment in order within pool[off, off+len). The matcher itself (LikePat,
+ * parse_like, like_find_byte, like_match) lives in like_match.h, shared
+ * with the host hook tg_like_match_host below. */
+#include "like_match.h"
 
 __global__ void k_pool_like(const uint8_t* __restrict__ pool,
                             const int64_t* __restrict__ offs,
@@ -766,31 +706,32 @@ __global__ void k_pool_like_indexed(const int64_t* __restrict__ offs,
     }
 }
 
-static tg_status parse_like(const char* pattern, LikePat* p)
+/* parse + word the rejection (TG_ERR_UNSUPPORTED: the pattern is legal SQL
+ * that this matcher does not implement) */
+static tg_status like_parse_checked(const char* pattern, LikePat* p)
 {
-    memset(p, 0, sizeof(*p));
-    size_t L = strlen(pattern);
-    if (L >= LIKE_MAX_PAT) { TG_SET_ERR("pattern too long"); return TG_ERR_UNSUPPORTED; }
-    p->anchor_start = L > 0 && pattern[0] != '%';
-    p->anchor_end = L > 0 && pattern[L - 1] != '%';
-    int n = 0, bo = 0;
-    const char* q = pattern;
-    while (*q) {
-        while (*q == '%') q++;
-        if (!*q) break;
-        const char* e = q;
-        while (*e && *e != '%') {
-            if (*e == '_') { TG_SET_ERR("'_' wildcard unsupported"); return TG_ERR_UNSUPPORTED; }
-            e++;
-        }
-        if (n >= LIKE_MAX_SEGS) { TG_SET_ERR("too many %% segments"); return TG_ERR_UNSUPPORTED; }
-        p->seg_off[n] = bo; p->seg_len[n] = (int)(e - q);
-        memcpy(p->bytes + bo, q, e - q);
-        bo += (int)(e - q);
-        n++;
-        q = e;
+    switch (parse_like(pattern, p)) {
+        case LIKE_PARSE_OK: return TG_OK;
+        case LIKE_PARSE_TOO_LONG: TG_SET_ERR("pattern too long"); break;
+        case LIKE_PARSE_UNDERSCORE: TG_SET_ERR("'_' wildcard unsupported"); break;
+        default: TG_SET_ERR("too many %% segments"); break;
     }
-    p->n_segs = n;
+    return TG_ERR_UNSUPPORTED;
+}
+
+/* host-only hook for tests and host drivers: *out = (bytes[0, len) LIKE
+ * pattern) through the very matcher the kernels run; no session, no GPU */
+extern "C" tg_status tg_like_match_host(const char* pattern,
+    const uint8_t* bytes, int32_t len, int32_t* out)
+{
+    if (!pattern || !out || len < 0 || (!bytes && len > 0)) {
+        TG_SET_ERR("tg_like_match_host: null argument or negative length");
+        return TG_ERR_INVALID_ARG;
+    }
+    LikePat p;
+    tg_status st = like_parse_checked(pattern, &p);
+    if (st != TG_OK) return st;
+    *out = like_match(bytes, len, p) ? 1 : 0;
     return TG_OK;
 }
 
@@ -798,11 +739,18 @@ static tg_status parse_like(const char* pattern, LikePat* p)
 extern "C" tg_status tg_pool_like_flags(tg_session* s, const int64_t* d_offs,
     const int32_t* d_lens, int64_t n, const char* pattern, uint8_t* d_flags)
 {
-    const uint8_t* d_pool = nullptr;
-    tg_status st = tg_tpch_pool(s, &d_pool);
-    if (st != TG_OK) return st;
+    /* every check happens before the first launch or allocation: a
+     * rejected call leaves d_flags untouched */
+    if (!s || !pattern || n < 0 || !d_offs || !d_lens || !d_flags) {
+        TG_SET_ERR("tg_pool_like_flags: null argument or negative row count");
+        return TG_ERR_INVALID_ARG;
+    }
     LikePat p;
-    st = parse_like(pattern, &p);
+    tg_status st = like_parse_checked(pattern, &p);
+    if (st != TG_OK) return st;
+    if (n == 0) return TG_OK;
+    const uint8_t* d_pool = nullptr;
+    st = tg_tpch_pool(s, &d_pool);
     if (st != TG_OK) return st;
     /* TG_LIKE_IDX: 0 = per-row byte scan, 1 = occurrence index,
      * 2 = offset-sorted byte scan (default above 1M rows — A/B in
@@ -886,9 +834,14 @@ extern "C" tg_status tg_pool_like_flags(tg_session* s, const int64_t* d_offs,
 extern "C" tg_status tg_varchar_like_flags(tg_session* s, const uint8_t* d_bytes,
     const int32_t* d_offsets, int64_t n, const char* pattern, uint8_t* d_flags)
 {
+    if (!s || !pattern || n < 0 || !d_bytes || !d_offsets || !d_flags) {
+        TG_SET_ERR("tg_varchar_like_flags: null argument or negative row count");
+        return TG_ERR_INVALID_ARG;
+    }
     LikePat p;
-    tg_status st = parse_like(pattern, &p);
+    tg_status st = like_parse_checked(pattern, &p);
     if (st != TG_OK) return st;
+    if (n == 0) return TG_OK;
     hipLaunchKernelGGL(k_var_like, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0,
                        s->stream, d_bytes, d_offsets, n, p, d_flags);
     TG_HIP_CHECK(hipGetLastError());
