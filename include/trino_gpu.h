@@ -537,6 +537,72 @@ tg_status tg_topn_create(tg_session*,
     const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
     int32_t limit, tg_operator** out);
 
+/* ---- Window (operator/WindowOperator.java): ranking functions and running
+ * aggregates OVER (PARTITION BY ... ORDER BY ...) ----
+ * Pages accumulate as in TopN. At finish the operator emits ONE page: every
+ * input channel, then one BIGINT channel per spec, in spec order. No input
+ * rows: no page, and `finished` is set.
+ *
+ * Row order: by the partition channels ASC NULLS LAST (what WindowOperator
+ * hands PagesIndex.sort), then by the sort channels under sort_desc with
+ * TopN's rule exactly (ASC nulls last, DESC nulls first, NaN the largest
+ * non-NULL value, -0.0 == 0.0). Rows whose whole partition-plus-sort key ties
+ * KEEP INPUT ORDER (page order, then row order), so every output is
+ * reproducible bit for bit, row_number and ROWS frames among peers included.
+ * The sort always runs on the device; there is no row threshold.
+ *
+ * Two adjacent sorted rows share a partition iff they agree on every
+ * partition channel under grouping equality: NULL is a value, all NaNs are
+ * one value, -0.0 is 0.0. They are peers iff they also agree on every sort
+ * channel under the same equality. n_partition == 0: one partition of
+ * everything. n_sort == 0: every row of a partition is a peer of every other.
+ * Both zero: no sort runs at all.
+ *
+ * ROW_NUMBER: 1-based position in the partition. RANK: the row_number of the
+ * row's first peer. DENSE_RANK: the number of peer groups up to and including
+ * the row's own. The three ignore input_channel (pass -1), require frame == 0
+ * and their output has no validity bitmap.
+ *
+ * Aggregates run over the frame. COUNT_STAR counts rows (input_channel is
+ * ignored). COUNT_COL counts the non-NULL cells of input_channel; neither
+ * count has a bitmap. SUM_I64 / MIN_I64 / MAX_I64 read an integer-typed
+ * channel (BIGINT, INTEGER, DATE, SMALLINT, TINYINT, BOOLEAN) widened to i64
+ * and skip NULLs; their output always carries a validity bitmap, and a frame
+ * that holds no non-NULL input gives NULL. SUM overflow wraps (undefined, like
+ * the expression lane). FRAME_RANGE gives every row of a peer group the value
+ * at the group's last row, FRAME_PARTITION the value at the partition's last
+ * row.
+ *
+ * Rejected before anything is launched: a null session / types / out, a null
+ * array with a non-zero count, n_specs outside 1..8, a partition / sort /
+ * input channel outside the channels, an unknown fn or frame, a ranking spec
+ * with frame != 0: TG_ERR_INVALID_ARG. Any VARCHAR channel (the payload
+ * gather moves fixed-width cells, as TopN), or a DOUBLE input_channel (a
+ * parallel scan reassociates the additions; an exact fixed-point running sum
+ * is a later change): TG_ERR_UNSUPPORTED. At add_input, a page with fewer
+ * channels than declared or with cell widths that differ from `types`:
+ * TG_ERR_INVALID_ARG.
+ *
+ * Out of scope: lag / lead / first_value / nth_value, bounded frames, DOUBLE
+ * aggregates, VARCHAR payloads, a TopNRanking cut-off. */
+typedef enum {
+    TG_WIN_ROW_NUMBER = 0, TG_WIN_RANK = 1, TG_WIN_DENSE_RANK = 2,
+    TG_WIN_COUNT_STAR = 3, TG_WIN_COUNT_COL = 4,
+    TG_WIN_SUM_I64 = 5, TG_WIN_MIN_I64 = 6, TG_WIN_MAX_I64 = 7
+} tg_window_fn;
+typedef enum {
+    TG_WIN_FRAME_RANGE = 0,     /* RANGE UNBOUNDED PRECEDING .. CURRENT ROW: the row's peers included (SQL default) */
+    TG_WIN_FRAME_ROWS = 1,      /* ROWS  UNBOUNDED PRECEDING .. CURRENT ROW */
+    TG_WIN_FRAME_PARTITION = 2  /* UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING */
+} tg_window_frame;
+typedef struct tg_window_spec { int32_t fn, input_channel, frame, _pad; } tg_window_spec;
+
+tg_status tg_window_create(tg_session*,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* partition_channels, int32_t n_partition,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    const tg_window_spec* specs, int32_t n_specs, tg_operator** out);
+
 /* ---- semi join (operator/HashSemiJoinOperator.java): appends a BOOLEAN
  * matched channel to the probe page. Three-valued IN: a hit is true; a NULL
  * probe key is false against a build of zero rows and NULL otherwise; a miss

@@ -1,0 +1,726 @@
+/* ops_window.hip — Window operator (operator/WindowOperator.java analog).
+ *
+ * Accumulates input pages like TopN; at finish it sorts every row on the
+ * device by (partition channels ASC NULLS LAST, sort channels), marks the
+ * partition and peer-group starts, and computes every window function as a
+ * SEGMENTED SCAN of i64 values plus, for the RANGE and whole-partition
+ * frames, a gather through the index of the segment's last row. One output
+ * page: the input channels in sorted order, then one BIGINT channel per spec.
+ *
+ * The segmented scan is the hot path. It is an inclusive scan
+ * under the associative pair operator
+ *     (f1,v1) (+) (f2,v2) = (f1|f2, f2 ? v2 : op(v1,v2))
+ * with op one of + / min / max on i64, built like run_scan_i32 as three
+ * launches: a wave per WSCAN_CHUNK rows reduces its chunk to one carry pair,
+ * the carries are scanned by the same operator (one wave up to
+ * WSCAN_ONE_WAVE entries, recursion above), and the same chunk pass runs
+ * again with each chunk's incoming carry. No block waits on another block:
+ * no look-back, no flag polling, no atomics, no fences; integer + / min / max
+ * give the same bits under any association, so the result is bit-exact.
+ */
+#include "sort_keys.h"
+#include "operators.h"
+#include <climits>
+
+#define WSCAN_CHUNK 1024
+#define WSCAN_ONE_WAVE 1024
+#define WSCAN_BATCH 4      /* 64-row groups loaded ahead of their scan */
+
+enum { WOP_ADD = 0, WOP_MIN = 1, WOP_MAX = 2 };
+/* where the scanned value of a position comes from */
+enum {
+    WSRC_ARRAY = 0,    /* vals[i] */
+    WSRC_ONE = 1,      /* 1 */
+    WSRC_INDEX = 2,    /* i */
+    WSRC_FLAG = 3,     /* (flags[i] & val_mask) ? 1 : 0 */
+    WSRC_MASKED = 4,   /* (flags[i] & val_mask) ? vals[i] : 0 */
+    WSRC_NEUTRAL = 5   /* aux[i] ? vals[i] : identity(op)   (NULL-neutralised) */
+};
+enum { WFLAG_PARTITION = 1, WFLAG_PEER = 2 };
+
+/* one scan's input. A head flag is (flags[i] & head_mask) != 0; position 0 is
+ * always a head. `reverse` scans from the last row towards the first with a
+ * head wherever the forward segmentation ENDS (the next row is a head), which
+ * turns a max scan of WSRC_INDEX into "index of my segment's last row". */
+struct WscanIn {
+    const int64_t* vals;
+    const int64_t* aux;
+    const uint8_t* flags;
+    int64_t n;
+    int32_t head_mask, val_mask, src, op, reverse;
+};
+
+__device__ static inline int64_t wscan_identity(int32_t op)
+{
+    return op == WOP_ADD ? 0 : op == WOP_MIN ? INT64_MAX : INT64_MIN;
+}
+
+__device__ static inline int64_t wscan_op(int32_t op, int64_t a, int64_t b)
+{
+    if (op == WOP_ADD) return (int64_t)((uint64_t)a + (uint64_t)b);   /* wraps */
+    if (op == WOP_MIN) return a < b ? a : b;
+    return a > b ? a : b;
+}
+
+/* physical index of logical scan position p */
+__device__ static inline int64_t wscan_phys(const WscanIn& in, int64_t p)
+{
+    return in.reverse ? in.n - 1 - p : p;
+}
+
+__device__ static inline void wscan_load(const WscanIn& in, int64_t p, int& f, int64_t& v)
+{
+    int64_t i = wscan_phys(in, p);
+    int fl = in.flags[i];
+    if (in.reverse) f = (i == in.n - 1) || (in.flags[i + 1] & in.head_mask);
+    else f = (i == 0) || (fl & in.head_mask);
+    switch (in.src) {
+        case WSRC_ARRAY: v = in.vals[i]; break;
+        case WSRC_ONE: v = 1; break;
+        case WSRC_INDEX: v = i; break;
+        case WSRC_FLAG: v = (fl & in.val_mask) ? 1 : 0; break;
+        case WSRC_MASKED: v = (fl & in.val_mask) ? in.vals[i] : 0; break;
+        default: v = in.aux[i] ? in.vals[i] : wscan_identity(in.op); break;
+    }
+}
+
+/* the chunk pass: one wave walks logical positions [lo, hi) in 64-row groups.
+ * Inside a group the pair operator runs as six __shfl_up steps on the values
+ * alone. The flag half of the pair needs no shuffle: one __ballot gives every
+ * lane the group's heads, hence `start`, the lane of the nearest head at or
+ * before it (-1: none), and "no head between the two lanes" (f2 == 0 of the
+ * pair being appended) is `lane - off >= start`. A lane whose partner lies
+ * before its head already holds its whole segment. (rf, rv) is the running
+ * pair carried from group to group (and, in the apply launch, into the chunk
+ * from the scanned carries); it reaches exactly the lanes with start < 0.
+ * lo and hi are wave-uniform, so every lane takes every shuffle. Lanes past
+ * hi hold (0, identity) and so copy their left neighbour: lane 63 always
+ * ends with the group's total. */
+template <bool WRITE>
+__device__ static inline void wscan_chunk(const WscanIn& in, int64_t lo, int64_t hi,
+                                          int lane, int& rf, int64_t& rv, int64_t* out)
+{
+    const int32_t op = in.op;
+    /* WSCAN_BATCH groups are loaded before the first of them is scanned, so
+     * a wave keeps that many loads in flight instead of paying one memory
+     * round trip per group; a group wholly past hi is (0, identity) in every
+     * lane and passes the running pair through unchanged */
+    for (int64_t g = lo; g < hi; g += 64 * WSCAN_BATCH) {
+        int fs[WSCAN_BATCH];
+        int64_t vs[WSCAN_BATCH];
+        #pragma unroll
+        for (int k = 0; k < WSCAN_BATCH; k++) {
+            int64_t p = g + 64 * k + lane;
+            fs[k] = 0;
+            vs[k] = wscan_identity(op);
+            if (p < hi) wscan_load(in, p, fs[k], vs[k]);
+        }
+        #pragma unroll
+        for (int k = 0; k < WSCAN_BATCH; k++) {
+            int64_t p = g + 64 * k + lane;
+            int64_t v = vs[k];
+            uint64_t heads = __ballot(fs[k]);
+            uint64_t mine = heads & (~0ull >> (63 - lane));     /* heads in lanes 0..lane */
+            int start = mine ? 63 - __clzll((long long)mine) : -1;
+            #pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                int64_t ov = (int64_t)__shfl_up((long long)v, off, 64);
+                if (lane >= off && lane - off >= start) v = wscan_op(op, ov, v);
+            }
+            if (start < 0) v = wscan_op(op, rv, v);
+            if (WRITE && p < hi) out[wscan_phys(in, p)] = v;
+            rv = (int64_t)__shfl((long long)v, 63, 64);
+            rf |= heads != 0;
+        }
+    }
+}
+
+/* launch 1: chunk c -> carry pair (carry_f[c], carry_v[c]) */
+__global__ void k_wscan_reduce(WscanIn in, int64_t nchunks,
+                               uint8_t* __restrict__ carry_f, int64_t* __restrict__ carry_v)
+{
+    int64_t c = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    if (c >= nchunks) return;
+    int lane = threadIdx.x % 64;
+    int64_t lo = c * WSCAN_CHUNK, hi = min(lo + (int64_t)WSCAN_CHUNK, in.n);
+    int rf = 0;
+    int64_t rv = wscan_identity(in.op);
+    wscan_chunk<false>(in, lo, hi, lane, rf, rv, nullptr);
+    if (lane == 0) {
+        carry_f[c] = rf ? 1 : 0;
+        carry_v[c] = rv;
+    }
+}
+
+/* launch 3: the chunk pass again, starting from the inclusive scan of the
+ * carries before chunk c */
+__global__ void k_wscan_apply(WscanIn in, int64_t nchunks,
+                              const int64_t* __restrict__ carry_scanned, int64_t* out)
+{
+    int64_t c = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    if (c >= nchunks) return;
+    int lane = threadIdx.x % 64;
+    int64_t lo = c * WSCAN_CHUNK, hi = min(lo + (int64_t)WSCAN_CHUNK, in.n);
+    int rf = 0;
+    int64_t rv = c ? carry_scanned[c - 1] : wscan_identity(in.op);
+    wscan_chunk<true>(in, lo, hi, lane, rf, rv, out);
+}
+
+/* the whole input by one wave (n <= WSCAN_ONE_WAVE) */
+__global__ void k_wscan_one_wave(WscanIn in, int64_t* out)
+{
+    if (blockIdx.x || threadIdx.x >= 64) return;
+    int rf = 0;
+    int64_t rv = wscan_identity(in.op);
+    wscan_chunk<true>(in, 0, in.n, threadIdx.x, rf, rv, out);
+}
+
+/* pool scratch of one emit: freed together, on every path, after the stream
+ * has drained (the kernels that use it are asynchronous) */
+struct WinScratch {
+    tg_session* s;
+    std::vector<void*> bufs;
+    explicit WinScratch(tg_session* s_) : s(s_) {}
+    WinScratch(const WinScratch&) = delete;
+    WinScratch& operator=(const WinScratch&) = delete;
+    template <typename T>
+    tg_status alloc(T** out, int64_t bytes)
+    {
+        void* p = nullptr;
+        tg_status st = tg_pool_alloc(s, &p, (size_t)(bytes > 0 ? bytes : 1));
+        if (st != TG_OK) return st;
+        bufs.push_back(p);
+        *out = (T*)p;
+        return TG_OK;
+    }
+    ~WinScratch()
+    {
+        (void)hipStreamSynchronize(s->stream);
+        for (void* p : bufs) tg_pool_free(s, p);
+    }
+};
+
+#define WIN_TRY(call) do { tg_status _ws = (call); if (_ws != TG_OK) return _ws; } while (0)
+
+/* inclusive segmented scan of `in` into out[n] (out may be in.vals). The
+ * flags are only read, so a level's flags serve both of its launches. */
+static tg_status run_wscan(tg_session* s, WinScratch& ws, const WscanIn& in, int64_t* out)
+{
+    if (in.n <= 0) return TG_OK;
+    if (in.n <= WSCAN_ONE_WAVE) {
+        hipLaunchKernelGGL(k_wscan_one_wave, dim3(1), dim3(64), 0, s->stream, in, out);
+        TG_HIP_CHECK(hipGetLastError());
+        return TG_OK;
+    }
+    int64_t nchunks = (in.n + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
+    uint8_t* carry_f = nullptr;
+    int64_t* carry_v = nullptr;
+    WIN_TRY(ws.alloc(&carry_f, nchunks));
+    WIN_TRY(ws.alloc(&carry_v, nchunks * 8));
+    int wpb = TG_BLOCK / 64;
+    dim3 grid((uint32_t)((nchunks + wpb - 1) / wpb)), block(TG_BLOCK);
+    hipLaunchKernelGGL(k_wscan_reduce, grid, block, 0, s->stream, in, nchunks,
+                       carry_f, carry_v);
+    TG_HIP_CHECK(hipGetLastError());
+    WscanIn up{};
+    up.vals = carry_v;
+    up.flags = carry_f;
+    up.n = nchunks;
+    up.head_mask = 1;
+    up.src = WSRC_ARRAY;
+    up.op = in.op;
+    WIN_TRY(run_wscan(s, ws, up, carry_v));
+    hipLaunchKernelGGL(k_wscan_apply, grid, block, 0, s->stream, in, nchunks,
+                       (const int64_t*)carry_v, out);
+    TG_HIP_CHECK(hipGetLastError());
+    return TG_OK;
+}
+
+/* key images of one ordering channel, indexed by flat input row */
+struct WinKey {
+    const uint64_t* kf;   /* topn_sortable image (0 where NULL) */
+    const uint64_t* nf;   /* null-pass bit; nullptr when the channel has no NULLs */
+};
+
+/* boundary flags of sorted position i against i-1: WFLAG_PARTITION where a
+ * partition channel differs, WFLAG_PEER where any channel differs. Equality
+ * is equality of image and null bit, i.e. grouping equality. keys[0..n_part)
+ * are the partition channels. Position 0 starts both. */
+__global__ void k_win_boundaries(const WinKey* __restrict__ keys, int32_t n_keys,
+                                 int32_t n_part, const int64_t* __restrict__ perm,
+                                 int64_t n, uint8_t* __restrict__ flags)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        int fl = 0;
+        if (i == 0) fl = WFLAG_PARTITION | WFLAG_PEER;
+        else {
+            int64_t a = perm[i - 1], b = perm[i];
+            for (int32_t j = 0; j < n_keys; j++) {
+                bool differ = keys[j].kf[a] != keys[j].kf[b] ||
+                              (keys[j].nf && keys[j].nf[a] != keys[j].nf[b]);
+                if (!differ) continue;
+                fl = (j < n_part) ? (WFLAG_PARTITION | WFLAG_PEER) : WFLAG_PEER;
+                break;   /* partition channels come first */
+            }
+        }
+        flags[i] = (uint8_t)fl;
+    }
+}
+
+/* aggregate input of one source page in sorted order, widened to i64:
+ * vals[o] (0 where NULL) and nonnull[o] (1 / 0) */
+template <typename T>
+__global__ void k_win_gather_input(const T* __restrict__ src,
+                                   const uint64_t* __restrict__ src_valid,
+                                   const int64_t* __restrict__ perm, int64_t total,
+                                   int64_t base, int64_t n, int64_t* __restrict__ vals,
+                                   int64_t* __restrict__ nonnull)
+{
+    int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; o < total; o += stride) {
+        int64_t r = perm[o] - base;
+        if (r < 0 || r >= n) continue;
+        bool ok = !src_valid || ((src_valid[r >> 6] >> (r & 63)) & 1);
+        vals[o] = ok ? (int64_t)src[r] : 0;
+        nonnull[o] = ok ? 1 : 0;
+    }
+}
+
+/* one spec's output column: row i takes the ROWS-frame result at e = end[i]
+ * (its own position when end is null); with `count` the cell is NULL unless
+ * count[e] > 0. A wave covers 64 aligned rows and writes their validity word
+ * with one ballot. */
+__global__ void k_win_emit(const int64_t* __restrict__ rows_result,
+                           const int64_t* __restrict__ count,
+                           const int64_t* __restrict__ end, int64_t n,
+                           int64_t* __restrict__ out, uint64_t* __restrict__ out_valid)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t n64 = (n + 63) & ~(int64_t)63;
+    for (; i < n64; i += stride) {
+        bool ok = false;
+        if (i < n) {
+            int64_t e = end ? end[i] : i;
+            ok = !count || count[e] > 0;
+            out[i] = ok ? rows_result[e] : 0;
+        }
+        if (out_valid) {
+            uint64_t w = __ballot(ok);
+            if ((threadIdx.x & 63) == 0) out_valid[i >> 6] = w;
+        }
+    }
+}
+
+struct WindowOp : tg_operator {
+    std::vector<tg_type> types;
+    std::vector<int32_t> partition_channels;
+    std::vector<int32_t> sort_channels;
+    std::vector<int32_t> sort_desc;     /* 0 asc, 1 desc */
+    std::vector<tg_window_spec> specs;
+    std::vector<DevPage> pages;
+    int64_t total_rows = 0;
+    bool emitted = false;
+
+    tg_status add_input(const tg_page* page) override
+    {
+        /* the output gather copies cells at the declared width */
+        if (page->channel_count < (int32_t)types.size()) {
+            TG_SET_ERR("window page has %d channels, operator %zu", page->channel_count, types.size());
+            return TG_ERR_INVALID_ARG;
+        }
+        for (size_t c = 0; c < types.size(); c++) {
+            DevBlock want, got;
+            want.type = types[c];
+            got.type = (tg_type)page->blocks[c].type;
+            if (got.type == TG_VARCHAR || got.elem_size() != want.elem_size()) {
+                TG_SET_ERR("window channel %zu type %d, operator declared %d", c,
+                           page->blocks[c].type, (int)types[c]);
+                return TG_ERR_INVALID_ARG;
+            }
+        }
+        DevPage in;
+        tg_status st = tg_upload_page(s, page, &in);
+        if (st != TG_OK) return st;
+        total_rows += in.n;
+        pages.emplace_back(std::move(in));
+        return TG_OK;
+    }
+
+    static bool is_ranking(int32_t fn) { return fn <= TG_WIN_DENSE_RANK; }
+    static bool has_validity(int32_t fn) { return fn >= TG_WIN_SUM_I64; }
+
+    /* stable LSD radix passes over partition then sort channels, starting
+     * from an iota: whole-key ties keep input order. The key images stay
+     * alive in the scratch and are listed in host_keys for the boundary
+     * kernel. */
+    tg_status sort_rows(WinScratch& ws, const std::vector<int64_t>& page_base,
+                        int64_t* d_perm, std::vector<WinKey>* host_keys)
+    {
+        size_t np = partition_channels.size(), k = np + sort_channels.size();
+        hipLaunchKernelGGL(k_iota_topn, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
+                           0, s->stream, d_perm, total_rows);
+        TG_HIP_CHECK(hipGetLastError());
+        if (!k) return TG_OK;
+        std::vector<uint64_t*> kf(k, nullptr), nf(k, nullptr);
+        for (size_t j = 0; j < k; j++) {
+            int32_t ch = j < np ? partition_channels[j] : sort_channels[j - np];
+            int32_t desc = j < np ? 0 : (sort_desc[j - np] != 0);
+            WIN_TRY(ws.alloc(&kf[j], total_rows * 8));
+            bool nullable = false;
+            for (auto& pg : pages) nullable |= pg.n && pg.blocks[ch].valid;
+            if (nullable) WIN_TRY(ws.alloc(&nf[j], total_rows * 8));
+            for (size_t p = 0; p < pages.size(); p++) {
+                const DevBlock& b = pages[p].blocks[ch];
+                if (!pages[p].n) continue;
+                hipLaunchKernelGGL(k_topn_keys, dim3(tg_grid_for(pages[p].n)),
+                                   dim3(TG_BLOCK), 0, s->stream, b.data, b.valid,
+                                   (int32_t)b.type, desc, pages[p].n,
+                                   kf[j] + page_base[p]);
+                TG_HIP_CHECK(hipGetLastError());
+                if (!nullable) continue;
+                hipLaunchKernelGGL(k_topn_null_keys, dim3(tg_grid_for(pages[p].n)),
+                                   dim3(TG_BLOCK), 0, s->stream, b.valid,
+                                   desc, pages[p].n, nf[j] + page_base[p]);
+                TG_HIP_CHECK(hipGetLastError());
+            }
+            host_keys->push_back(WinKey{kf[j], nf[j]});
+        }
+        uint64_t* d_keys = nullptr;
+        WIN_TRY(ws.alloc(&d_keys, total_rows * 8));
+        for (int j = (int)k - 1; j >= 0; j--) {
+            hipLaunchKernelGGL(k_gather_u64_by_perm, dim3(tg_grid_for(total_rows)),
+                               dim3(TG_BLOCK), 0, s->stream, kf[j], d_perm,
+                               total_rows, d_keys);
+            TG_HIP_CHECK(hipGetLastError());
+            WIN_TRY(run_sort_pairs(s, d_keys, d_perm, total_rows));
+            if (!nf[j]) continue;
+            /* the channel's major order: NULL or not, one stable 1-bit pass */
+            hipLaunchKernelGGL(k_gather_u64_by_perm, dim3(tg_grid_for(total_rows)),
+                               dim3(TG_BLOCK), 0, s->stream, nf[j], d_perm,
+                               total_rows, d_keys);
+            TG_HIP_CHECK(hipGetLastError());
+            WIN_TRY(run_sort_pairs_bits(s, d_keys, d_perm, total_rows, 1));
+        }
+        return TG_OK;
+    }
+
+    /* aggregate input of channel ch in sorted order */
+    tg_status gather_input(WinScratch& ws, const std::vector<int64_t>& page_base,
+                           const int64_t* d_perm, int32_t ch, int64_t** vals_out,
+                           int64_t** nonnull_out)
+    {
+        int64_t *vals = nullptr, *nonnull = nullptr;
+        WIN_TRY(ws.alloc(&vals, total_rows * 8));
+        WIN_TRY(ws.alloc(&nonnull, total_rows * 8));
+        dim3 grid(tg_grid_for(total_rows)), block(TG_BLOCK);
+        for (size_t p = 0; p < pages.size(); p++) {
+            const DevBlock& sb = pages[p].blocks[ch];
+            int64_t pn = pages[p].n;
+            if (!pn) continue;
+            switch (sb.elem_size()) {
+                case 8: hipLaunchKernelGGL(k_win_gather_input<int64_t>, grid, block, 0, s->stream,
+                            (const int64_t*)sb.data, sb.valid, d_perm, total_rows, page_base[p],
+                            pn, vals, nonnull); break;
+                case 4: hipLaunchKernelGGL(k_win_gather_input<int32_t>, grid, block, 0, s->stream,
+                            (const int32_t*)sb.data, sb.valid, d_perm, total_rows, page_base[p],
+                            pn, vals, nonnull); break;
+                case 2: hipLaunchKernelGGL(k_win_gather_input<int16_t>, grid, block, 0, s->stream,
+                            (const int16_t*)sb.data, sb.valid, d_perm, total_rows, page_base[p],
+                            pn, vals, nonnull); break;
+                default: hipLaunchKernelGGL(k_win_gather_input<int8_t>, grid, block, 0, s->stream,
+                            (const int8_t*)sb.data, sb.valid, d_perm, total_rows, page_base[p],
+                            pn, vals, nonnull); break;
+            }
+            TG_HIP_CHECK(hipGetLastError());
+        }
+        *vals_out = vals;
+        *nonnull_out = nonnull;
+        return TG_OK;
+    }
+
+    /* every input channel through the final permutation, validity included */
+    tg_status gather_payload(const std::vector<int64_t>& page_base, const int64_t* d_perm,
+                             DevPage* outp)
+    {
+        int64_t take = total_rows;
+        for (size_t c = 0; c < types.size(); c++) {
+            outp->blocks.emplace_back();
+            DevBlock& b = outp->blocks.back();
+            b.type = types[c];
+            b.n = take;
+            TG_POOL_ALLOC(s, &b.data, take * b.elem_size());
+            bool nullable = false;
+            for (auto& pg : pages) nullable |= pg.n && pg.blocks[c].valid;
+            if (nullable) {
+                int64_t words = (take + 63) / 64;
+                TG_POOL_ALLOC(s, &b.valid, words * 8);
+                TG_HIP_CHECK(hipMemsetAsync(b.valid, 0xFF, words * 8, s->stream));
+            }
+            for (size_t p = 0; p < pages.size(); p++) {
+                const DevBlock& sb = pages[p].blocks[c];
+                int64_t pn = pages[p].n;
+                if (!pn) continue;
+                dim3 grid(tg_grid_for(take)), block(TG_BLOCK);
+                switch (b.elem_size()) {
+                    case 8: hipLaunchKernelGGL(k_topn_gather<int64_t>, grid, block, 0, s->stream,
+                                (const int64_t*)sb.data, sb.valid, d_perm, take, page_base[p], pn,
+                                (int64_t*)b.data, b.valid); break;
+                    case 4: hipLaunchKernelGGL(k_topn_gather<int32_t>, grid, block, 0, s->stream,
+                                (const int32_t*)sb.data, sb.valid, d_perm, take, page_base[p], pn,
+                                (int32_t*)b.data, b.valid); break;
+                    case 2: hipLaunchKernelGGL(k_topn_gather<int16_t>, grid, block, 0, s->stream,
+                                (const int16_t*)sb.data, sb.valid, d_perm, take, page_base[p], pn,
+                                (int16_t*)b.data, b.valid); break;
+                    default: hipLaunchKernelGGL(k_topn_gather<int8_t>, grid, block, 0, s->stream,
+                                (const int8_t*)sb.data, sb.valid, d_perm, take, page_base[p], pn,
+                                (int8_t*)b.data, b.valid); break;
+                }
+                TG_HIP_CHECK(hipGetLastError());
+            }
+        }
+        return TG_OK;
+    }
+
+    tg_status emit_into(WinScratch& ws, DevPage* outp)
+    {
+        const int64_t n = total_rows;
+        std::vector<int64_t> page_base(pages.size() + 1, 0);
+        for (size_t p = 0; p < pages.size(); p++)
+            page_base[p + 1] = page_base[p] + pages[p].n;
+
+        int64_t* d_perm = nullptr;
+        WIN_TRY(ws.alloc(&d_perm, n * 8));
+        std::vector<WinKey> host_keys;
+        WIN_TRY(sort_rows(ws, page_base, d_perm, &host_keys));
+
+        /* partition-start and peer-start bits of every sorted position */
+        uint8_t* d_flags = nullptr;
+        WinKey* d_keytab = nullptr;
+        WIN_TRY(ws.alloc(&d_flags, n));
+        WIN_TRY(ws.alloc(&d_keytab, (int64_t)(host_keys.size() * sizeof(WinKey))));
+        if (!host_keys.empty()) {
+            TG_HIP_CHECK(hipMemcpyAsync(d_keytab, host_keys.data(),
+                                        host_keys.size() * sizeof(WinKey),
+                                        hipMemcpyHostToDevice, s->stream));
+            TG_HIP_CHECK(hipStreamSynchronize(s->stream));   /* host_keys is a local */
+        }
+        hipLaunchKernelGGL(k_win_boundaries, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0,
+                           s->stream, (const WinKey*)d_keytab, (int32_t)host_keys.size(),
+                           (int32_t)partition_channels.size(), (const int64_t*)d_perm, n,
+                           d_flags);
+        TG_HIP_CHECK(hipGetLastError());
+
+        outp->n = n;
+        WIN_TRY(gather_payload(page_base, d_perm, outp));
+
+        /* intermediates shared by the specs, each computed at most once */
+        int64_t* d_rownum = nullptr;
+        int64_t* d_end[3] = {nullptr, nullptr, nullptr};       /* by frame */
+        struct Input { int64_t *vals, *nonnull, *count; };
+        std::map<int32_t, Input> inputs;                        /* by channel */
+
+        auto scan = [&](int32_t src, int32_t op, int32_t head_mask, int32_t val_mask,
+                        const int64_t* vals, const int64_t* aux, int32_t reverse,
+                        int64_t* out) {
+            WscanIn in{};
+            in.vals = vals;
+            in.aux = aux;
+            in.flags = d_flags;
+            in.n = n;
+            in.head_mask = head_mask;
+            in.val_mask = val_mask;
+            in.src = src;
+            in.op = op;
+            in.reverse = reverse;
+            return run_wscan(s, ws, in, out);
+        };
+        auto rownum = [&]() -> tg_status {
+            if (d_rownum) return TG_OK;
+            WIN_TRY(ws.alloc(&d_rownum, n * 8));
+            return scan(WSRC_ONE, WOP_ADD, WFLAG_PARTITION, 0, nullptr, nullptr, 0, d_rownum);
+        };
+        /* index of the last row of the peer group (RANGE) or partition */
+        auto frame_end = [&](int32_t frame) -> tg_status {
+            if (frame == TG_WIN_FRAME_ROWS || d_end[frame]) return TG_OK;
+            WIN_TRY(ws.alloc(&d_end[frame], n * 8));
+            int32_t mask = frame == TG_WIN_FRAME_RANGE ? WFLAG_PEER : WFLAG_PARTITION;
+            return scan(WSRC_INDEX, WOP_MAX, mask, 0, nullptr, nullptr, 1, d_end[frame]);
+        };
+        auto input = [&](int32_t ch) -> tg_status {
+            if (inputs.count(ch)) return TG_OK;
+            Input in{nullptr, nullptr, nullptr};
+            WIN_TRY(gather_input(ws, page_base, d_perm, ch, &in.vals, &in.nonnull));
+            WIN_TRY(ws.alloc(&in.count, n * 8));
+            WIN_TRY(scan(WSRC_ARRAY, WOP_ADD, WFLAG_PARTITION, 0, in.nonnull, nullptr, 0,
+                         in.count));
+            inputs[ch] = in;
+            return TG_OK;
+        };
+
+        for (const tg_window_spec& sp : specs) {
+            outp->blocks.emplace_back();
+            DevBlock& b = outp->blocks.back();
+            b.type = TG_BIGINT;
+            b.n = n;
+            TG_POOL_ALLOC(s, &b.data, n * 8);
+            if (has_validity(sp.fn)) TG_POOL_ALLOC(s, &b.valid, ((n + 63) / 64) * 8);
+            int64_t* out = (int64_t*)b.data;
+            if (sp.fn == TG_WIN_RANK) {
+                WIN_TRY(rownum());
+                WIN_TRY(scan(WSRC_MASKED, WOP_MAX, WFLAG_PARTITION, WFLAG_PEER, d_rownum,
+                             nullptr, 0, out));
+                continue;
+            }
+            if (sp.fn == TG_WIN_DENSE_RANK) {
+                WIN_TRY(scan(WSRC_FLAG, WOP_ADD, WFLAG_PARTITION, WFLAG_PEER, nullptr,
+                             nullptr, 0, out));
+                continue;
+            }
+            /* the ROWS-frame result, then the frame's gather */
+            const int64_t* rows_result = nullptr;
+            const int64_t* count = nullptr;
+            if (sp.fn == TG_WIN_ROW_NUMBER || sp.fn == TG_WIN_COUNT_STAR) {
+                WIN_TRY(rownum());
+                rows_result = d_rownum;
+            }
+            else {
+                WIN_TRY(input(sp.input_channel));
+                const Input& in = inputs[sp.input_channel];
+                if (sp.fn == TG_WIN_COUNT_COL) rows_result = in.count;
+                else {
+                    int32_t op = sp.fn == TG_WIN_SUM_I64 ? WOP_ADD
+                               : sp.fn == TG_WIN_MIN_I64 ? WOP_MIN : WOP_MAX;
+                    int64_t* r = nullptr;
+                    WIN_TRY(ws.alloc(&r, n * 8));
+                    WIN_TRY(scan(WSRC_NEUTRAL, op, WFLAG_PARTITION, 0, in.vals, in.nonnull,
+                                 0, r));
+                    rows_result = r;
+                    count = in.count;
+                }
+            }
+            /* row_number has no frame: its frame field is 0 by contract */
+            int32_t frame = sp.fn == TG_WIN_ROW_NUMBER ? TG_WIN_FRAME_ROWS : sp.frame;
+            WIN_TRY(frame_end(frame));
+            hipLaunchKernelGGL(k_win_emit, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0, s->stream,
+                               rows_result, count, (const int64_t*)d_end[frame], n, out,
+                               b.valid);
+            TG_HIP_CHECK(hipGetLastError());
+        }
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        return TG_OK;
+    }
+
+    tg_status emit()
+    {
+        if (total_rows) {
+            DevPage outp;
+            tg_status st;
+            {
+                WinScratch ws(s);
+                st = emit_into(ws, &outp);
+            }   /* the scratch is back in the pool, the stream drained */
+            if (st != TG_OK) {
+                tg_free_page(s, &outp);
+                return st;
+            }
+            stage_output(std::move(outp));
+        }
+        for (auto& p : pages) tg_free_page(s, &p);
+        pages.clear();
+        return TG_OK;
+    }
+
+    tg_status get_output(tg_page* out, int* finished) override
+    {
+        if (input_finished && !emitted) {
+            emitted = true;
+            tg_status st = emit();
+            if (st != TG_OK) return st;
+        }
+        emit_staged(out, finished);
+        return TG_OK;
+    }
+
+    ~WindowOp() override
+    {
+        for (auto& p : pages) tg_free_page(s, &p);
+        for (auto& p : out_pages_) tg_free_page(s, &p);
+    }
+};
+
+extern "C" tg_status tg_window_create(tg_session* s,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* partition_channels, int32_t n_partition,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    const tg_window_spec* specs, int32_t n_specs, tg_operator** out)
+{
+    if (!s || !types || !out || n_channels < 1 || n_partition < 0 || n_sort < 0 ||
+        (n_partition && !partition_channels) || (n_sort && (!sort_channels || !sort_desc)) ||
+        !specs) {
+        TG_SET_ERR("invalid window spec: null argument or negative count");
+        return TG_ERR_INVALID_ARG;
+    }
+    if (n_specs < 1 || n_specs > 8) {
+        TG_SET_ERR("window: %d specs, 1..8 supported", n_specs);
+        return TG_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n_partition; i++)
+        if (partition_channels[i] < 0 || partition_channels[i] >= n_channels) {
+            TG_SET_ERR("window partition channel %d outside %d channels",
+                       partition_channels[i], n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+    for (int i = 0; i < n_sort; i++)
+        if (sort_channels[i] < 0 || sort_channels[i] >= n_channels) {
+            TG_SET_ERR("window sort channel %d outside %d channels", sort_channels[i], n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+    for (int i = 0; i < n_specs; i++) {
+        const tg_window_spec& sp = specs[i];
+        if (sp.fn < TG_WIN_ROW_NUMBER || sp.fn > TG_WIN_MAX_I64) {
+            TG_SET_ERR("window spec %d: unknown function %d", i, sp.fn);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (sp.frame < TG_WIN_FRAME_RANGE || sp.frame > TG_WIN_FRAME_PARTITION) {
+            TG_SET_ERR("window spec %d: unknown frame %d", i, sp.frame);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (WindowOp::is_ranking(sp.fn) && sp.frame != TG_WIN_FRAME_RANGE) {
+            TG_SET_ERR("window spec %d: ranking function %d takes frame 0, not %d", i,
+                       sp.fn, sp.frame);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (sp.fn >= TG_WIN_COUNT_COL &&
+            (sp.input_channel < 0 || sp.input_channel >= n_channels)) {
+            TG_SET_ERR("window spec %d: input channel %d outside %d channels", i,
+                       sp.input_channel, n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+    }
+    /* the payload gather moves fixed-width cells only (as TopN) */
+    for (int i = 0; i < n_channels; i++)
+        if (types[i] == TG_VARCHAR) {
+            TG_SET_ERR("window: VARCHAR channel %d is not supported", i);
+            return TG_ERR_UNSUPPORTED;
+        }
+    /* a parallel scan reassociates the additions: exact for integers only */
+    for (int i = 0; i < n_specs; i++)
+        if (specs[i].fn >= TG_WIN_COUNT_COL && types[specs[i].input_channel] == TG_DOUBLE) {
+            TG_SET_ERR("window spec %d: DOUBLE input channel %d is not supported", i,
+                       specs[i].input_channel);
+            return TG_ERR_UNSUPPORTED;
+        }
+    auto* op = new WindowOp();
+    op->s = s;
+    for (int i = 0; i < n_channels; i++) op->types.push_back((tg_type)types[i]);
+    op->partition_channels.assign(partition_channels, partition_channels + n_partition);
+    op->sort_channels.assign(sort_channels, sort_channels + n_sort);
+    op->sort_desc.assign(sort_desc, sort_desc + n_sort);
+    op->specs.assign(specs, specs + n_specs);
+    *out = op;
+    return TG_OK;
+}

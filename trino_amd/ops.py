@@ -444,6 +444,46 @@ def topn(session, types, sort_channels, sort_desc, limit):
     return op
 
 
+(WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT_STAR, WIN_COUNT_COL,
+ WIN_SUM_I64, WIN_MIN_I64, WIN_MAX_I64) = range(8)
+WIN_FRAME_RANGE, WIN_FRAME_ROWS, WIN_FRAME_PARTITION = range(3)
+
+
+class TgWindowSpec(ctypes.Structure):
+    _fields_ = [("fn", ctypes.c_int32), ("input_channel", ctypes.c_int32),
+                ("frame", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+_lib.tg_window_create.restype = ctypes.c_int
+_lib.tg_window_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                  ctypes.c_void_p, ctypes.c_int32,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+
+
+def window(session, types, partition_channels, sort_channels, sort_desc, specs):
+    """Window operator (operator/WindowOperator analog). specs: a list of
+    (fn, input_channel, frame) with the WIN_* / WIN_FRAME_* constants. The one
+    output page holds the input channels in sorted order, then one BIGINT
+    channel per spec."""
+    h = ctypes.c_void_p()
+    ty = _i32arr(types)
+    pc = _i32arr(partition_channels)
+    sc = _i32arr(sort_channels)
+    sd = _i32arr(sort_desc)
+    sp = (TgWindowSpec * max(len(specs), 1))()
+    for i, (fn, ch, frame) in enumerate(specs):
+        sp[i].fn, sp[i].input_channel, sp[i].frame = fn, ch, frame
+    _check(_lib.tg_window_create(
+        session._h, ty.ctypes.data, len(ty),
+        pc.ctypes.data if len(pc) else None, len(pc),
+        sc.ctypes.data if len(sc) else None, sd.ctypes.data if len(sd) else None, len(sc),
+        sp, len(specs), ctypes.byref(h)))
+    op = Operator(session, h)
+    op._keep = (ty, pc, sc, sd, sp)
+    return op
+
+
 def join_key_range(bridge):
     """Dynamic filter source: (min, max, non_null_rows) of the build keys."""
     mn = ctypes.c_int64()
