@@ -583,17 +583,25 @@ tg_status tg_topn_create(tg_session*,
  * channels than declared or with cell widths that differ from `types`:
  * TG_ERR_INVALID_ARG.
  *
- * Out of scope: lag / lead / first_value / nth_value, bounded frames, DOUBLE
- * aggregates, VARCHAR payloads, a TopNRanking cut-off. */
+ * tg_window_create takes functions 0..7 and frames 0..2 only; the functions
+ * and the frame below are reached through tg_window_create_ex.
+ *
+ * Out of scope: IGNORE NULLS, lag / lead defaults other than NULL, RANGE /
+ * GROUPS frames with offsets, DOUBLE aggregates, VARCHAR payloads, ntile /
+ * percent_rank / cume_dist, a TopNRanking cut-off. */
 typedef enum {
     TG_WIN_ROW_NUMBER = 0, TG_WIN_RANK = 1, TG_WIN_DENSE_RANK = 2,
     TG_WIN_COUNT_STAR = 3, TG_WIN_COUNT_COL = 4,
-    TG_WIN_SUM_I64 = 5, TG_WIN_MIN_I64 = 6, TG_WIN_MAX_I64 = 7
+    TG_WIN_SUM_I64 = 5, TG_WIN_MIN_I64 = 6, TG_WIN_MAX_I64 = 7,
+    /* tg_window_create_ex only */
+    TG_WIN_LAG = 8, TG_WIN_LEAD = 9, TG_WIN_FIRST_VALUE = 10,
+    TG_WIN_LAST_VALUE = 11, TG_WIN_NTH_VALUE = 12
 } tg_window_fn;
 typedef enum {
     TG_WIN_FRAME_RANGE = 0,     /* RANGE UNBOUNDED PRECEDING .. CURRENT ROW: the row's peers included (SQL default) */
     TG_WIN_FRAME_ROWS = 1,      /* ROWS  UNBOUNDED PRECEDING .. CURRENT ROW */
-    TG_WIN_FRAME_PARTITION = 2  /* UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING */
+    TG_WIN_FRAME_PARTITION = 2, /* UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING */
+    TG_WIN_FRAME_ROWS_BETWEEN = 3   /* ROWS BETWEEN frame_start AND frame_end; tg_window_create_ex only */
 } tg_window_frame;
 typedef struct tg_window_spec { int32_t fn, input_channel, frame, _pad; } tg_window_spec;
 
@@ -602,6 +610,70 @@ tg_status tg_window_create(tg_session*,
     const int32_t* partition_channels, int32_t n_partition,
     const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
     const tg_window_spec* specs, int32_t n_specs, tg_operator** out);
+
+/* ---- Window, second entry point: bounded ROWS frames and the value
+ * functions lag / lead / first_value / last_value / nth_value ----
+ * Row order, partition and peer rules, page accumulation, the single output
+ * page and the state machine are those of tg_window_create. A spec of the
+ * functions 0..7 under the frames 0..2 (frame_start, frame_end and offset
+ * zero) gives the same bits through either entry point.
+ *
+ * Frames. The frame of the row at sorted position i, in the partition
+ * [ps, pe], is the index range [lo, hi]:
+ *     FRAME_RANGE         lo = ps                        hi = the row's last peer
+ *     FRAME_ROWS          lo = ps                        hi = i
+ *     FRAME_PARTITION     lo = ps                        hi = pe
+ *     FRAME_ROWS_BETWEEN  lo = max(ps, i + frame_start)  hi = min(pe, i + frame_end)
+ * frame_start / frame_end are signed row offsets from the current row
+ * (-3 = 3 PRECEDING, 0 = CURRENT ROW, 2 = 2 FOLLOWING) or the UNBOUNDED
+ * values; i + offset saturates and never wraps, so frame_start = 2^62 and
+ * frame_end = INT64_MAX - 1 are legal. UNBOUNDED PRECEDING gives ps,
+ * UNBOUNDED FOLLOWING gives pe. lo > hi is an EMPTY frame: the offsets point
+ * past the partition's edge, or frame_start > frame_end (accepted; every
+ * frame is empty).
+ *
+ * Aggregates over FRAME_ROWS_BETWEEN: COUNT_STAR is max(0, hi - lo + 1),
+ * COUNT_COL the non-NULL cells of [lo, hi]; SUM_I64 / MIN_I64 / MAX_I64 skip
+ * NULLs, and an empty frame or one without a non-NULL cell gives NULL. The
+ * bitmap rule is unchanged: the three value aggregates carry one, the counts
+ * do not. SUM wraps and equals the wrapped sequential sum of the frame's
+ * cells.
+ *
+ * Value functions copy a cell of input_channel, any fixed-width type, DOUBLE
+ * included: NaN payloads and -0.0 come through bit for bit. The output
+ * channel has the input channel's type and width and always carries a
+ * validity bitmap. NULLs are respected: a NULL source cell is a NULL result.
+ *     LAG         the cell at i - offset if that is >= ps, else NULL; frame 0
+ *     LEAD        the cell at i + offset if that is <= pe, else NULL; frame 0
+ *     FIRST_VALUE the cell at lo; an empty frame gives NULL
+ *     LAST_VALUE  the cell at hi; an empty frame gives NULL
+ *     NTH_VALUE   the cell at lo + offset - 1 if that is <= hi, else NULL
+ * offset 0 of LAG / LEAD is the row itself; i + offset and lo + offset - 1
+ * saturate. FIRST / LAST / NTH_VALUE take any of the four frames.
+ *
+ * Rejected before anything is launched: everything tg_window_create rejects,
+ * with the same status; and with TG_ERR_INVALID_ARG: fn outside 0..12, frame
+ * outside 0..3, frame_start == UNBOUNDED_FOLLOWING, frame_end ==
+ * UNBOUNDED_PRECEDING, a non-zero frame_start / frame_end with a frame other
+ * than ROWS_BETWEEN, a non-zero offset on a function other than LAG / LEAD /
+ * NTH_VALUE, offset < 0 for LAG / LEAD, offset < 1 for NTH_VALUE, LAG / LEAD
+ * or a ranking function with frame != 0, a value function's input_channel
+ * outside the channels. TG_ERR_UNSUPPORTED: a DOUBLE input_channel on an
+ * aggregate, VARCHAR anywhere. */
+#define TG_WIN_UNBOUNDED_PRECEDING INT64_MIN
+#define TG_WIN_UNBOUNDED_FOLLOWING INT64_MAX
+typedef struct tg_window_spec_ex {
+    int32_t fn, input_channel, frame, _pad;
+    int64_t frame_start, frame_end; /* ROWS_BETWEEN only */
+    int64_t offset;                 /* LAG / LEAD: rows back / forward, >= 0;
+                                       NTH_VALUE: n >= 1; otherwise 0 */
+} tg_window_spec_ex;                /* 40 bytes */
+
+tg_status tg_window_create_ex(tg_session*,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* partition_channels, int32_t n_partition,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    const tg_window_spec_ex* specs, int32_t n_specs, tg_operator** out);
 
 /* ---- semi join (operator/HashSemiJoinOperator.java): appends a BOOLEAN
  * matched channel to the probe page. Three-valued IN: a hit is true; a NULL

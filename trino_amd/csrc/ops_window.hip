@@ -17,10 +17,21 @@
  * again with each chunk's incoming carry. No block waits on another block:
  * no look-back, no flag polling, no atomics, no fences; integer + / min / max
  * give the same bits under any association, so the result is bit-exact.
+ *
+ * On top of that sits the frame layer of tg_window_create_ex:
+ * every frame becomes an index range [lo, hi] per row (k_win_bounds); counts
+ * and sums over ROWS BETWEEN are differences of the partition-headed scans
+ * (k_win_frame_emit), min / max over a frame open at one end is a forward or
+ * reverse scan read at the other end, min / max over a frame bounded at both
+ * ends is a sparse table evaluated level by level (k_win_level), and lag /
+ * lead / first_value / last_value / nth_value are one gather of the sorted
+ * payload cells (k_win_value). The output channel of a value function has its
+ * input channel's type.
  */
 #include "sort_keys.h"
 #include "operators.h"
 #include <climits>
+#include <tuple>
 
 #define WSCAN_CHUNK 1024
 #define WSCAN_ONE_WAVE 1024
@@ -315,12 +326,185 @@ __global__ void k_win_emit(const int64_t* __restrict__ rows_result,
     }
 }
 
+/* ---- the frame layer: bounded ROWS frames and the value
+ * functions. Every frame is an index range [lo, hi] of sorted positions
+ * inside the row's partition; an empty frame is stored as (0, -1). ---- */
+
+/* a + b for a >= 0, saturating at INT64_MAX (b < 0 cannot wrap) */
+__device__ static inline int64_t win_sat_add(int64_t a, int64_t b)
+{
+    return b > INT64_MAX - a ? INT64_MAX : a + b;
+}
+
+/* frame bounds of every sorted position. ps = i - row_number + 1; `end` is
+ * the frame's end index per row for RANGE (last peer) and PARTITION (pe),
+ * the partition end for ROWS_BETWEEN, unused for ROWS. */
+__global__ void k_win_bounds(int32_t frame, int64_t start, int64_t stop,
+                             const int64_t* __restrict__ rownum,
+                             const int64_t* __restrict__ end, int64_t n,
+                             int64_t* __restrict__ lo, int64_t* __restrict__ hi)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        int64_t l = i - rownum[i] + 1, h = i;
+        if (frame == TG_WIN_FRAME_ROWS_BETWEEN) {
+            l = max(l, win_sat_add(i, start));
+            h = min(end[i], win_sat_add(i, stop));
+            if (l > h) {
+                l = 0;
+                h = -1;
+            }
+        }
+        else if (frame != TG_WIN_FRAME_ROWS) h = end[i];
+        lo[i] = l;
+        hi[i] = h;
+    }
+}
+
+/* non-NULL cells of [l, h], a non-empty frame of the partition that starts
+ * at ps, from the partition-headed inclusive count */
+__device__ static inline int64_t win_frame_count(const int64_t* __restrict__ count,
+                                                 int64_t ps, int64_t l, int64_t h)
+{
+    return count[h] - (l > ps ? count[l - 1] : 0);
+}
+
+enum {
+    WFE_DIFF = 0,      /* S[hi] - S[lo-1] of a partition-headed scan (wrapping);
+                          S null: the frame's row count */
+    WFE_AT_HI = 1,     /* S[hi]: a forward min / max scan, frame starts at ps */
+    WFE_AT_LO = 2      /* S[lo]: a reverse min / max scan, frame ends at pe */
+};
+
+/* one aggregate column over [lo, hi] from scans that exist already. With
+ * out_valid the cell is NULL unless the frame holds a non-NULL input. */
+__global__ void k_win_frame_emit(int32_t mode, const int64_t* __restrict__ S,
+                                 const int64_t* __restrict__ count,
+                                 const int64_t* __restrict__ lo,
+                                 const int64_t* __restrict__ hi,
+                                 const int64_t* __restrict__ rownum, int64_t n,
+                                 int64_t* __restrict__ out, uint64_t* __restrict__ out_valid)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t n64 = (n + 63) & ~(int64_t)63;
+    for (; i < n64; i += stride) {
+        bool ok = false;
+        if (i < n) {
+            int64_t l = lo[i], h = hi[i], ps = i - rownum[i] + 1, v = 0;
+            if (l <= h) {
+                ok = !out_valid || win_frame_count(count, ps, l, h) > 0;
+                if (mode == WFE_AT_HI) v = S[h];
+                else if (mode == WFE_AT_LO) v = S[l];
+                else if (!S) v = h - l + 1;
+                else v = (int64_t)((uint64_t)S[h] - (uint64_t)(l > ps ? S[l - 1] : 0));
+            }
+            else ok = !out_valid;      /* an empty frame counts 0 */
+            out[i] = ok ? v : 0;
+        }
+        if (out_valid) {
+            uint64_t w = __ballot(ok);
+            if ((threadIdx.x & 63) == 0) out_valid[i >> 6] = w;
+        }
+    }
+}
+
+/* sliding min / max over frames bounded at both ends: one level of a sparse
+ * table that is never stored. T_0 is the input with NULLs replaced by the
+ * identity and T_k[i] = op(T_{k-1}[i], T_{k-1}[i + 2^(k-1)]) covers
+ * [i, i + 2^k). Launch k reads T_k (launch 0 reads vals / nonnull), answers
+ * every row whose frame length L has floor(log2 L) == k with
+ * op(T_k[lo], T_k[hi - 2^k + 1]), and writes T_{k+1} when a later level needs
+ * it. The table is not segmented: a frame never leaves its partition, so no
+ * query reads a window that does. Launch 0 also writes the whole validity
+ * bitmap and the 0 of every NULL cell; later launches read their row's bit.
+ * Reads and writes of one launch touch different arrays, and the kernel
+ * boundary is the only synchronisation. */
+__global__ void k_win_level(int32_t k, int32_t op, const int64_t* __restrict__ T,
+                            const int64_t* __restrict__ nonnull, int64_t* __restrict__ Tnext,
+                            const int64_t* __restrict__ count,
+                            const int64_t* __restrict__ lo, const int64_t* __restrict__ hi,
+                            const int64_t* __restrict__ rownum, int64_t n,
+                            int64_t* __restrict__ out, uint64_t* __restrict__ out_valid)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t n64 = (n + 63) & ~(int64_t)63;
+    const int64_t ident = wscan_identity(op), w = (int64_t)1 << k;
+    /* nonnull is given at level 0 only: T is then the raw input */
+    auto cell = [&](int64_t j) { return !nonnull || nonnull[j] ? T[j] : ident; };
+    for (; i < n64; i += stride) {
+        bool ok = false;
+        if (i < n) {
+            int64_t l = lo[i], h = hi[i], len = h - l + 1;
+            if (k == 0) {
+                ok = len > 0 && win_frame_count(count, i - rownum[i] + 1, l, h) > 0;
+                if (!ok) out[i] = 0;
+            }
+            else ok = (out_valid[i >> 6] >> (i & 63)) & 1;
+            if (ok && len >= w && (len >> 1) < w)
+                out[i] = wscan_op(op, cell(l), cell(h - w + 1));
+            if (Tnext) Tnext[i] = wscan_op(op, cell(i), i + w < n ? cell(i + w) : ident);
+        }
+        if (k == 0) {
+            uint64_t b = __ballot(ok);
+            if ((threadIdx.x & 63) == 0) out_valid[i >> 6] = b;
+        }
+    }
+}
+
+enum { WVAL_LAG = 0, WVAL_LEAD = 1, WVAL_FIRST = 2, WVAL_LAST = 3, WVAL_NTH = 4 };
+
+/* value functions: row i copies the sorted-order cell at an index computed
+ * from its frame (FIRST / LAST / NTH: lo, hi) or its partition (LAG: rownum,
+ * LEAD: pend); NULL when the index falls outside or the source cell is NULL.
+ * The cells are copied at their own width, bit for bit. */
+template <typename T>
+__global__ void k_win_value(int32_t mode, int64_t offset, const T* __restrict__ src,
+                            const uint64_t* __restrict__ src_valid,
+                            const int64_t* __restrict__ lo, const int64_t* __restrict__ hi,
+                            const int64_t* __restrict__ rownum,
+                            const int64_t* __restrict__ pend, int64_t n,
+                            T* __restrict__ out, uint64_t* __restrict__ out_valid)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t n64 = (n + 63) & ~(int64_t)63;
+    for (; i < n64; i += stride) {
+        bool ok = false;
+        if (i < n) {
+            int64_t at = -1;
+            if (mode == WVAL_LAG) {
+                int64_t j = i - offset;          /* offset >= 0: cannot wrap */
+                if (j >= i - rownum[i] + 1) at = j;
+            }
+            else if (mode == WVAL_LEAD) {
+                int64_t j = win_sat_add(i, offset);
+                if (j <= pend[i]) at = j;
+            }
+            else {
+                int64_t l = lo[i], h = hi[i];
+                if (l <= h) {
+                    int64_t j = mode == WVAL_FIRST ? l : mode == WVAL_LAST ? h
+                              : win_sat_add(l, offset - 1);
+                    if (j <= h) at = j;
+                }
+            }
+            ok = at >= 0 && (!src_valid || ((src_valid[at >> 6] >> (at & 63)) & 1));
+            out[i] = ok ? src[at] : (T)0;
+        }
+        uint64_t w = __ballot(ok);
+        if ((threadIdx.x & 63) == 0) out_valid[i >> 6] = w;
+    }
+}
+
 struct WindowOp : tg_operator {
     std::vector<tg_type> types;
     std::vector<int32_t> partition_channels;
     std::vector<int32_t> sort_channels;
     std::vector<int32_t> sort_desc;     /* 0 asc, 1 desc */
-    std::vector<tg_window_spec> specs;
+    std::vector<tg_window_spec_ex> specs;
     std::vector<DevPage> pages;
     int64_t total_rows = 0;
     bool emitted = false;
@@ -352,6 +536,45 @@ struct WindowOp : tg_operator {
 
     static bool is_ranking(int32_t fn) { return fn <= TG_WIN_DENSE_RANK; }
     static bool has_validity(int32_t fn) { return fn >= TG_WIN_SUM_I64; }
+    static bool is_value_fn(int32_t fn) { return fn >= TG_WIN_LAG; }
+    static bool is_aggregate(int32_t fn) { return fn >= TG_WIN_COUNT_COL && fn <= TG_WIN_MAX_I64; }
+
+    /* launches of k_win_level for ROWS BETWEEN start AND stop over n rows: a
+     * frame holds at most min(stop - start + 1, n) rows, and a frame of L
+     * rows is answered at level floor(log2 L). One launch always runs: it
+     * writes the bitmap. */
+    static int32_t window_levels(int64_t start, int64_t stop, int64_t n)
+    {
+        if (stop < start) return 1;
+        uint64_t width = (uint64_t)stop - (uint64_t)start + 1;     /* no wrap: both bounded */
+        uint64_t longest = width < (uint64_t)n ? width : (uint64_t)n;
+        int32_t levels = 1;
+        while (longest >>= 1) levels++;
+        return levels;
+    }
+
+    tg_status launch_value(int32_t mode, int64_t offset, const DevBlock& src,
+                           const int64_t* lo, const int64_t* hi, const int64_t* rn,
+                           const int64_t* pend, DevBlock& b)
+    {
+        dim3 grid(tg_grid_for(total_rows)), block(TG_BLOCK);
+        switch (b.elem_size()) {
+            case 8: hipLaunchKernelGGL(k_win_value<int64_t>, grid, block, 0, s->stream, mode, offset,
+                        (const int64_t*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
+                        total_rows, (int64_t*)b.data, b.valid); break;
+            case 4: hipLaunchKernelGGL(k_win_value<int32_t>, grid, block, 0, s->stream, mode, offset,
+                        (const int32_t*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
+                        total_rows, (int32_t*)b.data, b.valid); break;
+            case 2: hipLaunchKernelGGL(k_win_value<int16_t>, grid, block, 0, s->stream, mode, offset,
+                        (const int16_t*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
+                        total_rows, (int16_t*)b.data, b.valid); break;
+            default: hipLaunchKernelGGL(k_win_value<int8_t>, grid, block, 0, s->stream, mode, offset,
+                        (const int8_t*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
+                        total_rows, (int8_t*)b.data, b.valid); break;
+        }
+        TG_HIP_CHECK(hipGetLastError());
+        return TG_OK;
+    }
 
     /* stable LSD radix passes over partition then sort channels, starting
      * from an iota: whole-key ties keep input order. The key images stay
@@ -561,14 +784,123 @@ struct WindowOp : tg_operator {
             return TG_OK;
         };
 
-        for (const tg_window_spec& sp : specs) {
+        /* the frame layer's intermediates, each at most once per operator:
+         * [lo, hi] per distinct frame, and the NULL-neutralised partition-
+         * headed scans of an input by (channel, op, direction) */
+        struct Bounds { int64_t *lo, *hi; };
+        std::map<std::tuple<int32_t, int64_t, int64_t>, Bounds> bounds;
+        std::map<std::tuple<int32_t, int32_t, int32_t>, int64_t*> runnings;
+        auto frame_bounds = [&](const tg_window_spec_ex& sp, Bounds* got) -> tg_status {
+            auto key = std::make_tuple(sp.frame, sp.frame_start, sp.frame_end);
+            auto it = bounds.find(key);
+            if (it != bounds.end()) {
+                *got = it->second;
+                return TG_OK;
+            }
+            /* ROWS_BETWEEN clamps at the partition end */
+            int32_t endf = sp.frame == TG_WIN_FRAME_ROWS_BETWEEN ? (int32_t)TG_WIN_FRAME_PARTITION
+                                                                 : sp.frame;
+            WIN_TRY(rownum());
+            WIN_TRY(frame_end(endf));
+            Bounds b{nullptr, nullptr};
+            WIN_TRY(ws.alloc(&b.lo, n * 8));
+            WIN_TRY(ws.alloc(&b.hi, n * 8));
+            hipLaunchKernelGGL(k_win_bounds, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0, s->stream,
+                               sp.frame, sp.frame_start, sp.frame_end,
+                               (const int64_t*)d_rownum, (const int64_t*)d_end[endf], n,
+                               b.lo, b.hi);
+            TG_HIP_CHECK(hipGetLastError());
+            bounds[key] = b;
+            *got = b;
+            return TG_OK;
+        };
+        auto running = [&](int32_t ch, int32_t op, int32_t reverse, int64_t** got) -> tg_status {
+            auto key = std::make_tuple(ch, op, reverse);
+            auto it = runnings.find(key);
+            if (it != runnings.end()) {
+                *got = it->second;
+                return TG_OK;
+            }
+            const Input& in = inputs[ch];
+            int64_t* r = nullptr;
+            WIN_TRY(ws.alloc(&r, n * 8));
+            WIN_TRY(scan(WSRC_NEUTRAL, op, WFLAG_PARTITION, 0, in.vals, in.nonnull, reverse, r));
+            runnings[key] = r;
+            *got = r;
+            return TG_OK;
+        };
+
+        for (const tg_window_spec_ex& sp : specs) {
             outp->blocks.emplace_back();
             DevBlock& b = outp->blocks.back();
-            b.type = TG_BIGINT;
+            b.type = is_value_fn(sp.fn) ? types[sp.input_channel] : TG_BIGINT;
             b.n = n;
-            TG_POOL_ALLOC(s, &b.data, n * 8);
+            TG_POOL_ALLOC(s, &b.data, n * b.elem_size());
             if (has_validity(sp.fn)) TG_POOL_ALLOC(s, &b.valid, ((n + 63) / 64) * 8);
             int64_t* out = (int64_t*)b.data;
+            if (is_value_fn(sp.fn)) {
+                /* the cells in sorted order are the payload channel itself */
+                const DevBlock& src = outp->blocks[sp.input_channel];
+                Bounds fb{nullptr, nullptr};
+                if (sp.fn == TG_WIN_LAG) WIN_TRY(rownum());
+                else if (sp.fn == TG_WIN_LEAD) WIN_TRY(frame_end(TG_WIN_FRAME_PARTITION));
+                else WIN_TRY(frame_bounds(sp, &fb));
+                WIN_TRY(launch_value(sp.fn - TG_WIN_LAG, sp.offset, src, fb.lo, fb.hi, d_rownum,
+                                     d_end[TG_WIN_FRAME_PARTITION], b));
+                continue;
+            }
+            if (sp.frame == TG_WIN_FRAME_ROWS_BETWEEN) {
+                Bounds fb{nullptr, nullptr};
+                WIN_TRY(frame_bounds(sp, &fb));
+                dim3 grid(tg_grid_for(n)), block(TG_BLOCK);
+                if (sp.fn == TG_WIN_COUNT_STAR) {
+                    hipLaunchKernelGGL(k_win_frame_emit, grid, block, 0, s->stream,
+                                       (int32_t)WFE_DIFF, (const int64_t*)nullptr,
+                                       (const int64_t*)nullptr, (const int64_t*)fb.lo,
+                                       (const int64_t*)fb.hi, (const int64_t*)d_rownum, n, out,
+                                       (uint64_t*)nullptr);
+                    TG_HIP_CHECK(hipGetLastError());
+                    continue;
+                }
+                WIN_TRY(input(sp.input_channel));
+                const Input in = inputs[sp.input_channel];
+                int32_t op = sp.fn == TG_WIN_MIN_I64 ? WOP_MIN
+                           : sp.fn == TG_WIN_MAX_I64 ? WOP_MAX : WOP_ADD;
+                /* an offset that reaches past every partition is unbounded */
+                bool open_start = sp.frame_start <= -(n - 1);
+                bool open_end = sp.frame_end >= n - 1;
+                if (op == WOP_ADD || open_start || open_end) {
+                    /* prefix difference, or a min / max scan read at one end */
+                    int32_t mode = op == WOP_ADD ? WFE_DIFF : open_start ? WFE_AT_HI : WFE_AT_LO;
+                    const int64_t* S = in.count;
+                    if (sp.fn != TG_WIN_COUNT_COL) {
+                        int64_t* r = nullptr;
+                        WIN_TRY(running(sp.input_channel, op, mode == WFE_AT_LO, &r));
+                        S = r;
+                    }
+                    hipLaunchKernelGGL(k_win_frame_emit, grid, block, 0, s->stream, mode, S,
+                                       (const int64_t*)in.count, (const int64_t*)fb.lo,
+                                       (const int64_t*)fb.hi, (const int64_t*)d_rownum, n, out,
+                                       b.valid);
+                    TG_HIP_CHECK(hipGetLastError());
+                    continue;
+                }
+                /* sliding min / max: one launch per level of the widest frame */
+                int32_t levels = window_levels(sp.frame_start, sp.frame_end, n);
+                int64_t* T[2] = {nullptr, nullptr};
+                for (int t = 0; t < 2 && t < levels - 1; t++) WIN_TRY(ws.alloc(&T[t], n * 8));
+                for (int32_t k = 0; k < levels; k++) {
+                    const int64_t* src = k ? T[(k - 1) & 1] : in.vals;
+                    hipLaunchKernelGGL(k_win_level, grid, block, 0, s->stream, k, op, src,
+                                       (const int64_t*)(k ? nullptr : in.nonnull),
+                                       k + 1 < levels ? T[k & 1] : (int64_t*)nullptr,
+                                       (const int64_t*)in.count, (const int64_t*)fb.lo,
+                                       (const int64_t*)fb.hi, (const int64_t*)d_rownum, n, out,
+                                       b.valid);
+                    TG_HIP_CHECK(hipGetLastError());
+                }
+                continue;
+            }
             if (sp.fn == TG_WIN_RANK) {
                 WIN_TRY(rownum());
                 WIN_TRY(scan(WSRC_MASKED, WOP_MAX, WFLAG_PARTITION, WFLAG_PEER, d_rownum,
@@ -652,11 +984,20 @@ struct WindowOp : tg_operator {
     }
 };
 
-extern "C" tg_status tg_window_create(tg_session* s,
+static tg_window_spec_ex window_widen(const tg_window_spec& sp)
+{
+    return tg_window_spec_ex{sp.fn, sp.input_channel, sp.frame, 0, 0, 0, 0};
+}
+static tg_window_spec_ex window_widen(const tg_window_spec_ex& sp) { return sp; }
+
+/* both entry points: the same checks in the same order, with the functions
+ * and frames up to max_fn / max_frame */
+template <typename Spec>
+static tg_status window_create(tg_session* s,
     const int32_t* types, int32_t n_channels,
     const int32_t* partition_channels, int32_t n_partition,
     const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
-    const tg_window_spec* specs, int32_t n_specs, tg_operator** out)
+    const Spec* specs, int32_t n_specs, int32_t max_fn, int32_t max_frame, tg_operator** out)
 {
     if (!s || !types || !out || n_channels < 1 || n_partition < 0 || n_sort < 0 ||
         (n_partition && !partition_channels) || (n_sort && (!sort_channels || !sort_desc)) ||
@@ -679,25 +1020,48 @@ extern "C" tg_status tg_window_create(tg_session* s,
             TG_SET_ERR("window sort channel %d outside %d channels", sort_channels[i], n_channels);
             return TG_ERR_INVALID_ARG;
         }
+    std::vector<tg_window_spec_ex> wide;
+    for (int i = 0; i < n_specs; i++) wide.push_back(window_widen(specs[i]));
     for (int i = 0; i < n_specs; i++) {
-        const tg_window_spec& sp = specs[i];
-        if (sp.fn < TG_WIN_ROW_NUMBER || sp.fn > TG_WIN_MAX_I64) {
+        const tg_window_spec_ex& sp = wide[i];
+        if (sp.fn < TG_WIN_ROW_NUMBER || sp.fn > max_fn) {
             TG_SET_ERR("window spec %d: unknown function %d", i, sp.fn);
             return TG_ERR_INVALID_ARG;
         }
-        if (sp.frame < TG_WIN_FRAME_RANGE || sp.frame > TG_WIN_FRAME_PARTITION) {
+        if (sp.frame < TG_WIN_FRAME_RANGE || sp.frame > max_frame) {
             TG_SET_ERR("window spec %d: unknown frame %d", i, sp.frame);
             return TG_ERR_INVALID_ARG;
         }
-        if (WindowOp::is_ranking(sp.fn) && sp.frame != TG_WIN_FRAME_RANGE) {
-            TG_SET_ERR("window spec %d: ranking function %d takes frame 0, not %d", i,
-                       sp.fn, sp.frame);
+        bool positional = sp.fn == TG_WIN_LAG || sp.fn == TG_WIN_LEAD;
+        if ((WindowOp::is_ranking(sp.fn) || positional) && sp.frame != TG_WIN_FRAME_RANGE) {
+            TG_SET_ERR("window spec %d: %s function %d takes frame 0, not %d", i,
+                       positional ? "lag / lead" : "ranking", sp.fn, sp.frame);
             return TG_ERR_INVALID_ARG;
         }
         if (sp.fn >= TG_WIN_COUNT_COL &&
             (sp.input_channel < 0 || sp.input_channel >= n_channels)) {
             TG_SET_ERR("window spec %d: input channel %d outside %d channels", i,
                        sp.input_channel, n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (sp.frame != TG_WIN_FRAME_ROWS_BETWEEN && (sp.frame_start || sp.frame_end)) {
+            TG_SET_ERR("window spec %d: frame offsets with frame %d; only ROWS_BETWEEN takes them",
+                       i, sp.frame);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (sp.frame_start == TG_WIN_UNBOUNDED_FOLLOWING ||
+            sp.frame_end == TG_WIN_UNBOUNDED_PRECEDING) {
+            TG_SET_ERR("window spec %d: a frame starts at UNBOUNDED FOLLOWING or ends at "
+                       "UNBOUNDED PRECEDING", i);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (sp.offset && !positional && sp.fn != TG_WIN_NTH_VALUE) {
+            TG_SET_ERR("window spec %d: function %d takes no offset", i, sp.fn);
+            return TG_ERR_INVALID_ARG;
+        }
+        if ((positional && sp.offset < 0) || (sp.fn == TG_WIN_NTH_VALUE && sp.offset < 1)) {
+            TG_SET_ERR("window spec %d: offset %lld of function %d", i, (long long)sp.offset,
+                       sp.fn);
             return TG_ERR_INVALID_ARG;
         }
     }
@@ -707,11 +1071,12 @@ extern "C" tg_status tg_window_create(tg_session* s,
             TG_SET_ERR("window: VARCHAR channel %d is not supported", i);
             return TG_ERR_UNSUPPORTED;
         }
-    /* a parallel scan reassociates the additions: exact for integers only */
+    /* a parallel scan reassociates the additions: exact for integers only.
+     * The value functions copy cells and take a DOUBLE channel. */
     for (int i = 0; i < n_specs; i++)
-        if (specs[i].fn >= TG_WIN_COUNT_COL && types[specs[i].input_channel] == TG_DOUBLE) {
+        if (WindowOp::is_aggregate(wide[i].fn) && types[wide[i].input_channel] == TG_DOUBLE) {
             TG_SET_ERR("window spec %d: DOUBLE input channel %d is not supported", i,
-                       specs[i].input_channel);
+                       wide[i].input_channel);
             return TG_ERR_UNSUPPORTED;
         }
     auto* op = new WindowOp();
@@ -720,7 +1085,29 @@ extern "C" tg_status tg_window_create(tg_session* s,
     op->partition_channels.assign(partition_channels, partition_channels + n_partition);
     op->sort_channels.assign(sort_channels, sort_channels + n_sort);
     op->sort_desc.assign(sort_desc, sort_desc + n_sort);
-    op->specs.assign(specs, specs + n_specs);
+    op->specs = std::move(wide);
     *out = op;
     return TG_OK;
+}
+
+extern "C" tg_status tg_window_create(tg_session* s,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* partition_channels, int32_t n_partition,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    const tg_window_spec* specs, int32_t n_specs, tg_operator** out)
+{
+    return window_create(s, types, n_channels, partition_channels, n_partition, sort_channels,
+                         sort_desc, n_sort, specs, n_specs, TG_WIN_MAX_I64,
+                         TG_WIN_FRAME_PARTITION, out);
+}
+
+extern "C" tg_status tg_window_create_ex(tg_session* s,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* partition_channels, int32_t n_partition,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    const tg_window_spec_ex* specs, int32_t n_specs, tg_operator** out)
+{
+    return window_create(s, types, n_channels, partition_channels, n_partition, sort_channels,
+                         sort_desc, n_sort, specs, n_specs, TG_WIN_NTH_VALUE,
+                         TG_WIN_FRAME_ROWS_BETWEEN, out);
 }

@@ -484,6 +484,50 @@ def window(session, types, partition_channels, sort_channels, sort_desc, specs):
     return op
 
 
+(WIN_LAG, WIN_LEAD, WIN_FIRST_VALUE, WIN_LAST_VALUE, WIN_NTH_VALUE) = range(8, 13)
+WIN_FRAME_ROWS_BETWEEN = 3
+WIN_UNBOUNDED_PRECEDING = -2 ** 63
+WIN_UNBOUNDED_FOLLOWING = 2 ** 63 - 1
+
+
+class TgWindowSpecEx(ctypes.Structure):
+    _fields_ = [("fn", ctypes.c_int32), ("input_channel", ctypes.c_int32),
+                ("frame", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("frame_start", ctypes.c_int64), ("frame_end", ctypes.c_int64),
+                ("offset", ctypes.c_int64)]
+
+
+_lib.tg_window_create_ex.restype = ctypes.c_int
+_lib.tg_window_create_ex.argtypes = _lib.tg_window_create.argtypes
+
+
+def window_ex(session, types, partition_channels, sort_channels, sort_desc, specs):
+    """Window operator with bounded ROWS frames and the value functions.
+    specs: a list of (fn, input_channel, frame, frame_start, frame_end,
+    offset). frame_start / frame_end are signed row offsets from the current
+    row, or WIN_UNBOUNDED_PRECEDING / WIN_UNBOUNDED_FOLLOWING, under
+    WIN_FRAME_ROWS_BETWEEN and 0 otherwise; offset is the k of lag / lead and
+    the n of nth_value. A value function's output channel has its input
+    channel's type; every other spec gives a BIGINT channel."""
+    h = ctypes.c_void_p()
+    ty = _i32arr(types)
+    pc = _i32arr(partition_channels)
+    sc = _i32arr(sort_channels)
+    sd = _i32arr(sort_desc)
+    sp = (TgWindowSpecEx * max(len(specs), 1))()
+    for i, (fn, ch, frame, start, end, offset) in enumerate(specs):
+        sp[i].fn, sp[i].input_channel, sp[i].frame = fn, ch, frame
+        sp[i].frame_start, sp[i].frame_end, sp[i].offset = start, end, offset
+    _check(_lib.tg_window_create_ex(
+        session._h, ty.ctypes.data, len(ty),
+        pc.ctypes.data if len(pc) else None, len(pc),
+        sc.ctypes.data if len(sc) else None, sd.ctypes.data if len(sd) else None, len(sc),
+        sp, len(specs), ctypes.byref(h)))
+    op = Operator(session, h)
+    op._keep = (ty, pc, sc, sd, sp)
+    return op
+
+
 def join_key_range(bridge):
     """Dynamic filter source: (min, max, non_null_rows) of the build keys."""
     mn = ctypes.c_int64()
