@@ -877,7 +877,7 @@ class TestVarcharJoinAndGather:
 
 class TestTopNDevicePath:
     """n >= 65536 routes TopN through the device radix-sort path
-    (ops_topn.hip emit_device); parity vs numpy lexsort."""
+    (order_pages of sort.hip); parity vs numpy lexsort."""
 
     def test_large_topn_composite(self, sess, ops):
         r = rng(70)

@@ -33,6 +33,46 @@ struct DevPage {
     std::vector<DevBlock> blocks;
 };
 
+/* call f with a value of the integer type as wide as a fixed-width cell, so a
+ * generic lambda can launch kernel<decltype(t)>: cells move bit for bit */
+template <typename F>
+static inline auto tg_dispatch_width(int64_t elem_size, F&& f)
+{
+    switch (elem_size) {
+        case 8: return f(int64_t{});
+        case 4: return f(int32_t{});
+        case 2: return f(int16_t{});
+        default: return f(int8_t{});
+    }
+}
+
+#define TG_TRY(call) do { tg_status _ts = (call); if (_ts != TG_OK) return _ts; } while (0)
+
+/* pool temporaries of one piece of work: freed together, on every path, after
+ * the stream has drained (the kernels that use them are asynchronous) */
+struct PoolScratch {
+    tg_session* s;
+    std::vector<void*> bufs;
+    explicit PoolScratch(tg_session* s_) : s(s_) {}
+    PoolScratch(const PoolScratch&) = delete;
+    PoolScratch& operator=(const PoolScratch&) = delete;
+    template <typename T>
+    tg_status alloc(T** out, int64_t bytes)
+    {
+        void* p = nullptr;
+        tg_status st = tg_pool_alloc(s, &p, (size_t)(bytes > 0 ? bytes : 1));
+        if (st != TG_OK) return st;
+        bufs.push_back(p);
+        *out = (T*)p;
+        return TG_OK;
+    }
+    ~PoolScratch()
+    {
+        (void)hipStreamSynchronize(s->stream);
+        for (void* p : bufs) tg_pool_free(s, p);
+    }
+};
+
 /* upload a host/device tg_page into device-owned DevPage (flat memcpy of the
  * backing arrays; DictionaryBlock/RLE are decoded to flat values on upload —
  * the aggregation loops only need the flat ValueBlock forms, SURVEY.md §8

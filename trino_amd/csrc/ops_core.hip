@@ -141,13 +141,9 @@ tg_status tg_upload_page(tg_session* s, const tg_page* in, DevPage* out)
             }
         }
         else {
-            tg_status st;
-            switch (db->elem_size()) {
-                case 8: st = decode_to_flat<int64_t>(s, b, db); break;
-                case 4: st = decode_to_flat<int32_t>(s, b, db); break;
-                case 2: st = decode_to_flat<int16_t>(s, b, db); break;
-                default: st = decode_to_flat<int8_t>(s, b, db); break;
-            }
+            tg_status st = tg_dispatch_width(db->elem_size(), [&](auto t) {
+                return decode_to_flat<decltype(t)>(s, b, db);
+            });
             if (st != TG_OK) return st;
             if (b->dictionary && b->dictionary->valid) {
                 /* NULL dictionary entries: fold them into the row bitmap */

@@ -873,20 +873,12 @@ tg_status run_gather(tg_session* s, const DevBlock& src, const int32_t* d_positi
         TG_HIP_CHECK(hipMemsetAsync(out->valid, 0xFF, words * 8, s->stream));
     }
     int grid = tg_grid_for(count);
-    switch (src.elem_size()) {
-        case 8: hipLaunchKernelGGL(k_gather<int64_t>, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                    (const int64_t*)src.data, src.valid, d_positions, count,
-                    (int64_t*)out->data, out->valid); break;
-        case 4: hipLaunchKernelGGL(k_gather<int32_t>, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                    (const int32_t*)src.data, src.valid, d_positions, count,
-                    (int32_t*)out->data, out->valid); break;
-        case 2: hipLaunchKernelGGL(k_gather<int16_t>, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                    (const int16_t*)src.data, src.valid, d_positions, count,
-                    (int16_t*)out->data, out->valid); break;
-        default: hipLaunchKernelGGL(k_gather<int8_t>, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                    (const int8_t*)src.data, src.valid, d_positions, count,
-                    (int8_t*)out->data, out->valid); break;
-    }
+    tg_dispatch_width(src.elem_size(), [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_gather<T>, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
+                           (const T*)src.data, src.valid, d_positions, count,
+                           (T*)out->data, out->valid);
+    });
     TG_HIP_CHECK(hipGetLastError());
     TG_HIP_CHECK(hipStreamSynchronize(s->stream));
     return TG_OK;

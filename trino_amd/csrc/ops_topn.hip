@@ -4,15 +4,16 @@
  * keep the top `limit` rows under the given orderings, emit one page in order.
  * Orderings follow Trino's defaults: ASC = nulls last, DESC = nulls first.
  *
- * Round-1 shape: input pages stay device-resident; at finish the SORT-KEY
- * channels of the accumulated rows are brought to the host, a partial_sort
- * selects the top-limit indices (limit is small — Q3/most sweep tails use
- * LIMIT 10..100), and the output page is gathered on device. A device top-k
- * selection kernel replaces the host sort when limit*pages grows (tracked in
- * DESIGN.md §8f).
+ * Input pages stay device-resident. At finish the top-limit row indices are
+ * chosen on one of two paths. From 65536 accumulated rows up, the rows are
+ * ordered on the device (order_pages, sort_keys.h: a host partial_sort cost
+ * tens of ms at Q3's ~1.1M aggregated groups) and the head of the permutation
+ * is used where it lies. Below that, the sort-key channels are brought to the
+ * host, a partial_sort selects the indices and they are uploaded. Either way
+ * the output page is gathered on the device (gather_pages).
  */
 #include "dev_hash.h"
-#include "sort_keys.h"   /* topn_sortable, the key kernels and the gathers */
+#include "sort_keys.h"   /* the page check, order_pages, gather_pages */
 #include <algorithm>
 
 struct TopNOp : tg_operator {
@@ -26,24 +27,9 @@ struct TopNOp : tg_operator {
 
     tg_status add_input(const tg_page* page) override
     {
-        /* the output gather copies cells at the declared width */
-        if (page->channel_count < (int32_t)types.size()) {
-            TG_SET_ERR("topn page has %d channels, operator %zu", page->channel_count, types.size());
-            return TG_ERR_INVALID_ARG;
-        }
-        for (size_t c = 0; c < types.size(); c++) {
-            DevBlock want, got;
-            want.type = types[c];
-            got.type = (tg_type)page->blocks[c].type;
-            if (got.type == TG_VARCHAR || got.elem_size() != want.elem_size()) {
-                TG_SET_ERR("topn channel %zu type %d, operator declared %d", c,
-                           page->blocks[c].type, (int)types[c]);
-                return TG_ERR_INVALID_ARG;
-            }
-        }
+        TG_TRY(check_fixed_width_page("topn", page, types));
         DevPage in;
-        tg_status st = tg_upload_page(s, page, &in);
-        if (st != TG_OK) return st;
+        TG_TRY(tg_upload_page(s, page, &in));
         total_rows += in.n;
         pages.emplace_back(std::move(in));
         return TG_OK;
@@ -56,80 +42,51 @@ struct TopNOp : tg_operator {
         return total_rows >= 65536;
     }
 
-    /* device top-k: per-channel sortable-u64 keys, then stable radix passes
-     * least-significant key first (lexicographic), take the head of the
-     * final permutation. Replaces a host partial_sort that cost tens of ms
-     * at Q3's ~1.1M aggregated groups. */
-    tg_status emit_device(int64_t take, std::vector<int64_t>* idx)
+    /* the row indices on either path, then the output gather */
+    tg_status emit_into(PoolScratch& ps, int64_t take, DevPage* outp)
     {
-        size_t k = sort_channels.size();
-        std::vector<int64_t> page_base(pages.size() + 1, 0);
-        for (size_t p = 0; p < pages.size(); p++)
-            page_base[p + 1] = page_base[p] + pages[p].n;
-        std::vector<uint64_t*> kf(k, nullptr), nf(k, nullptr);
-        for (size_t j = 0; j < k; j++) {
-            TG_POOL_ALLOC(s, &kf[j], total_rows * 8);
-            bool nullable = false;
-            for (auto& pg : pages) nullable |= pg.n && pg.blocks[sort_channels[j]].valid;
-            if (nullable) TG_POOL_ALLOC(s, &nf[j], total_rows * 8);
-            for (size_t p = 0; p < pages.size(); p++) {
-                const DevBlock& b = pages[p].blocks[sort_channels[j]];
-                if (!pages[p].n) continue;
-                hipLaunchKernelGGL(k_topn_keys, dim3(tg_grid_for(pages[p].n)),
-                                   dim3(TG_BLOCK), 0, s->stream, b.data, b.valid,
-                                   (int32_t)b.type, sort_desc[j], pages[p].n,
-                                   kf[j] + page_base[p]);
-                TG_HIP_CHECK(hipGetLastError());
-                if (!nullable) continue;
-                hipLaunchKernelGGL(k_topn_null_keys, dim3(tg_grid_for(pages[p].n)),
-                                   dim3(TG_BLOCK), 0, s->stream, b.valid,
-                                   sort_desc[j], pages[p].n, nf[j] + page_base[p]);
-                TG_HIP_CHECK(hipGetLastError());
-            }
+        int64_t* d_idx = nullptr;
+        std::vector<int64_t> idx;      /* outlives its upload */
+        if (device_sortable()) {
+            std::vector<std::pair<int32_t, int32_t>> keys;
+            for (size_t j = 0; j < sort_channels.size(); j++)
+                keys.emplace_back(sort_channels[j], sort_desc[j]);
+            TG_TRY(ps.alloc(&d_idx, total_rows * 8));
+            TG_TRY(order_pages(s, ps, pages, total_rows, keys, d_idx, nullptr));
         }
-        int64_t* d_perm = nullptr;
-        uint64_t* d_keys = nullptr;
-        TG_POOL_ALLOC(s, &d_perm, total_rows * 8);
-        TG_POOL_ALLOC(s, &d_keys, total_rows * 8);
-        hipLaunchKernelGGL(k_iota_topn, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
-                           0, s->stream, d_perm, total_rows);
-        TG_HIP_CHECK(hipGetLastError());
-        for (int j = (int)k - 1; j >= 0; j--) {
-            hipLaunchKernelGGL(k_gather_u64_by_perm, dim3(tg_grid_for(total_rows)),
-                               dim3(TG_BLOCK), 0, s->stream, kf[j], d_perm,
-                               total_rows, d_keys);
-            TG_HIP_CHECK(hipGetLastError());
-            tg_status st = run_sort_pairs(s, d_keys, d_perm, total_rows);
-            if (st != TG_OK) return st;
-            if (!nf[j]) continue;
-            /* the channel's major order: NULL or not, one stable 1-bit pass */
-            hipLaunchKernelGGL(k_gather_u64_by_perm, dim3(tg_grid_for(total_rows)),
-                               dim3(TG_BLOCK), 0, s->stream, nf[j], d_perm,
-                               total_rows, d_keys);
-            TG_HIP_CHECK(hipGetLastError());
-            st = run_sort_pairs_bits(s, d_keys, d_perm, total_rows, 1);
-            if (st != TG_OK) return st;
+        else {
+            TG_TRY(host_order(take, &idx));
+            TG_TRY(ps.alloc(&d_idx, take * 8));
+            if (take)
+                TG_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), take * 8,
+                                            hipMemcpyHostToDevice, s->stream));
         }
-        idx->resize(take);
-        if (take) {
-            TG_HIP_CHECK(hipMemcpy(idx->data(), d_perm, take * 8,
-                                   hipMemcpyDeviceToHost));
-        }
-        for (size_t j = 0; j < k; j++) { tg_pool_free(s, kf[j]); tg_pool_free(s, nf[j]); }
-        tg_pool_free(s, d_perm);
-        tg_pool_free(s, d_keys);
+        TG_TRY(gather_pages(s, pages, types, d_idx, take, outp));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
         return TG_OK;
     }
 
     tg_status emit()
     {
-        if (device_sortable()) {
-            int64_t take = std::min<int64_t>(limit, total_rows);
-            std::vector<int64_t> idx;
-            tg_status st = emit_device(take, &idx);
-            if (st != TG_OK) return st;
-            return gather_out(take, idx);
+        DevPage outp;
+        tg_status st;
+        {
+            PoolScratch ps(s);
+            st = emit_into(ps, std::min<int64_t>(limit, total_rows), &outp);
         }
+        if (st != TG_OK) {
+            tg_free_page(s, &outp);
+            return st;
+        }
+        stage_output(std::move(outp));
+        for (auto& p : pages) tg_free_page(s, &p);
+        pages.clear();
+        return TG_OK;
+    }
+
+    /* the top `take` flat row indices in order, by a host partial_sort */
+    tg_status host_order(int64_t take, std::vector<int64_t>* out)
+    {
         /* concatenate sort channels on host */
         size_t k = sort_channels.size();
         std::vector<std::vector<double>> keys_f(k);
@@ -213,69 +170,11 @@ struct TopNOp : tg_operator {
             }
             return false;
         };
-        int64_t take = std::min<int64_t>(limit, total_rows);
-        std::vector<int64_t> idx(total_rows);
+        std::vector<int64_t>& idx = *out;
+        idx.resize(total_rows);
         for (int64_t i = 0; i < total_rows; i++) idx[i] = i;
         std::partial_sort(idx.begin(), idx.begin() + take, idx.end(), less);
         idx.resize(take);
-        return gather_out(take, idx);
-    }
-
-    tg_status gather_out(int64_t take, const std::vector<int64_t>& idx)
-    {
-        /* one gather launch per (channel, source page): each output slot
-         * finds its flat row in exactly one page; validity travels along */
-        std::vector<int64_t> page_base(pages.size() + 1, 0);
-        for (size_t p = 0; p < pages.size(); p++)
-            page_base[p + 1] = page_base[p] + pages[p].n;
-
-        int64_t* d_idx = nullptr;
-        TG_POOL_ALLOC(s, &d_idx, (take ? take : 1) * 8);
-        if (take)
-            TG_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), take * 8,
-                                        hipMemcpyHostToDevice, s->stream));
-        DevPage outp;
-        outp.n = take;
-        for (size_t c = 0; c < types.size(); c++) {
-            DevBlock b;
-            b.type = types[c];
-            b.n = take;
-            TG_POOL_ALLOC(s, &b.data, (take ? take : 1) * b.elem_size());
-            bool nullable = false;
-            for (auto& pg : pages) nullable |= pg.n && pg.blocks[c].valid;
-            if (nullable) {
-                int64_t words = (take + 63) / 64;
-                TG_POOL_ALLOC(s, &b.valid, (words ? words : 1) * 8);
-                TG_HIP_CHECK(hipMemsetAsync(b.valid, 0xFF, words * 8, s->stream));
-            }
-            for (size_t p = 0; take && p < pages.size(); p++) {
-                const DevBlock& sb = pages[p].blocks[c];
-                int64_t pn = pages[p].n;
-                if (!pn) continue;
-                dim3 grid(tg_grid_for(take)), block(TG_BLOCK);
-                switch (b.elem_size()) {
-                    case 8: hipLaunchKernelGGL(k_topn_gather<int64_t>, grid, block, 0, s->stream,
-                                (const int64_t*)sb.data, sb.valid, d_idx, take, page_base[p], pn,
-                                (int64_t*)b.data, b.valid); break;
-                    case 4: hipLaunchKernelGGL(k_topn_gather<int32_t>, grid, block, 0, s->stream,
-                                (const int32_t*)sb.data, sb.valid, d_idx, take, page_base[p], pn,
-                                (int32_t*)b.data, b.valid); break;
-                    case 2: hipLaunchKernelGGL(k_topn_gather<int16_t>, grid, block, 0, s->stream,
-                                (const int16_t*)sb.data, sb.valid, d_idx, take, page_base[p], pn,
-                                (int16_t*)b.data, b.valid); break;
-                    default: hipLaunchKernelGGL(k_topn_gather<int8_t>, grid, block, 0, s->stream,
-                                (const int8_t*)sb.data, sb.valid, d_idx, take, page_base[p], pn,
-                                (int8_t*)b.data, b.valid); break;
-                }
-                TG_HIP_CHECK(hipGetLastError());
-            }
-            outp.blocks.push_back(b);
-        }
-        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-        tg_pool_free(s, d_idx);
-        stage_output(std::move(outp));
-        for (auto& p : pages) tg_free_page(s, &p);
-        pages.clear();
         return TG_OK;
     }
 

@@ -186,36 +186,9 @@ __global__ void k_wscan_one_wave(WscanIn in, int64_t* out)
     wscan_chunk<true>(in, 0, in.n, threadIdx.x, rf, rv, out);
 }
 
-/* pool scratch of one emit: freed together, on every path, after the stream
- * has drained (the kernels that use it are asynchronous) */
-struct WinScratch {
-    tg_session* s;
-    std::vector<void*> bufs;
-    explicit WinScratch(tg_session* s_) : s(s_) {}
-    WinScratch(const WinScratch&) = delete;
-    WinScratch& operator=(const WinScratch&) = delete;
-    template <typename T>
-    tg_status alloc(T** out, int64_t bytes)
-    {
-        void* p = nullptr;
-        tg_status st = tg_pool_alloc(s, &p, (size_t)(bytes > 0 ? bytes : 1));
-        if (st != TG_OK) return st;
-        bufs.push_back(p);
-        *out = (T*)p;
-        return TG_OK;
-    }
-    ~WinScratch()
-    {
-        (void)hipStreamSynchronize(s->stream);
-        for (void* p : bufs) tg_pool_free(s, p);
-    }
-};
-
-#define WIN_TRY(call) do { tg_status _ws = (call); if (_ws != TG_OK) return _ws; } while (0)
-
 /* inclusive segmented scan of `in` into out[n] (out may be in.vals). The
  * flags are only read, so a level's flags serve both of its launches. */
-static tg_status run_wscan(tg_session* s, WinScratch& ws, const WscanIn& in, int64_t* out)
+static tg_status run_wscan(tg_session* s, PoolScratch& ws, const WscanIn& in, int64_t* out)
 {
     if (in.n <= 0) return TG_OK;
     if (in.n <= WSCAN_ONE_WAVE) {
@@ -226,8 +199,8 @@ static tg_status run_wscan(tg_session* s, WinScratch& ws, const WscanIn& in, int
     int64_t nchunks = (in.n + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
     uint8_t* carry_f = nullptr;
     int64_t* carry_v = nullptr;
-    WIN_TRY(ws.alloc(&carry_f, nchunks));
-    WIN_TRY(ws.alloc(&carry_v, nchunks * 8));
+    TG_TRY(ws.alloc(&carry_f, nchunks));
+    TG_TRY(ws.alloc(&carry_v, nchunks * 8));
     int wpb = TG_BLOCK / 64;
     dim3 grid((uint32_t)((nchunks + wpb - 1) / wpb)), block(TG_BLOCK);
     hipLaunchKernelGGL(k_wscan_reduce, grid, block, 0, s->stream, in, nchunks,
@@ -240,18 +213,15 @@ static tg_status run_wscan(tg_session* s, WinScratch& ws, const WscanIn& in, int
     up.head_mask = 1;
     up.src = WSRC_ARRAY;
     up.op = in.op;
-    WIN_TRY(run_wscan(s, ws, up, carry_v));
+    TG_TRY(run_wscan(s, ws, up, carry_v));
     hipLaunchKernelGGL(k_wscan_apply, grid, block, 0, s->stream, in, nchunks,
                        (const int64_t*)carry_v, out);
     TG_HIP_CHECK(hipGetLastError());
     return TG_OK;
 }
 
-/* key images of one ordering channel, indexed by flat input row */
-struct WinKey {
-    const uint64_t* kf;   /* topn_sortable image (0 where NULL) */
-    const uint64_t* nf;   /* null-pass bit; nullptr when the channel has no NULLs */
-};
+/* the key images of order_pages, as k_win_boundaries reads them */
+using WinKey = SortKeyImages;
 
 /* boundary flags of sorted position i against i-1: WFLAG_PARTITION where a
  * partition channel differs, WFLAG_PEER where any channel differs. Equality
@@ -511,24 +481,9 @@ struct WindowOp : tg_operator {
 
     tg_status add_input(const tg_page* page) override
     {
-        /* the output gather copies cells at the declared width */
-        if (page->channel_count < (int32_t)types.size()) {
-            TG_SET_ERR("window page has %d channels, operator %zu", page->channel_count, types.size());
-            return TG_ERR_INVALID_ARG;
-        }
-        for (size_t c = 0; c < types.size(); c++) {
-            DevBlock want, got;
-            want.type = types[c];
-            got.type = (tg_type)page->blocks[c].type;
-            if (got.type == TG_VARCHAR || got.elem_size() != want.elem_size()) {
-                TG_SET_ERR("window channel %zu type %d, operator declared %d", c,
-                           page->blocks[c].type, (int)types[c]);
-                return TG_ERR_INVALID_ARG;
-            }
-        }
+        TG_TRY(check_fixed_width_page("window", page, types));
         DevPage in;
-        tg_status st = tg_upload_page(s, page, &in);
-        if (st != TG_OK) return st;
+        TG_TRY(tg_upload_page(s, page, &in));
         total_rows += in.n;
         pages.emplace_back(std::move(in));
         return TG_OK;
@@ -558,106 +513,35 @@ struct WindowOp : tg_operator {
                            const int64_t* pend, DevBlock& b)
     {
         dim3 grid(tg_grid_for(total_rows)), block(TG_BLOCK);
-        switch (b.elem_size()) {
-            case 8: hipLaunchKernelGGL(k_win_value<int64_t>, grid, block, 0, s->stream, mode, offset,
-                        (const int64_t*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
-                        total_rows, (int64_t*)b.data, b.valid); break;
-            case 4: hipLaunchKernelGGL(k_win_value<int32_t>, grid, block, 0, s->stream, mode, offset,
-                        (const int32_t*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
-                        total_rows, (int32_t*)b.data, b.valid); break;
-            case 2: hipLaunchKernelGGL(k_win_value<int16_t>, grid, block, 0, s->stream, mode, offset,
-                        (const int16_t*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
-                        total_rows, (int16_t*)b.data, b.valid); break;
-            default: hipLaunchKernelGGL(k_win_value<int8_t>, grid, block, 0, s->stream, mode, offset,
-                        (const int8_t*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
-                        total_rows, (int8_t*)b.data, b.valid); break;
-        }
+        tg_dispatch_width(b.elem_size(), [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_win_value<T>, grid, block, 0, s->stream, mode, offset,
+                               (const T*)src.data, (const uint64_t*)src.valid, lo, hi, rn, pend,
+                               total_rows, (T*)b.data, b.valid);
+        });
         TG_HIP_CHECK(hipGetLastError());
-        return TG_OK;
-    }
-
-    /* stable LSD radix passes over partition then sort channels, starting
-     * from an iota: whole-key ties keep input order. The key images stay
-     * alive in the scratch and are listed in host_keys for the boundary
-     * kernel. */
-    tg_status sort_rows(WinScratch& ws, const std::vector<int64_t>& page_base,
-                        int64_t* d_perm, std::vector<WinKey>* host_keys)
-    {
-        size_t np = partition_channels.size(), k = np + sort_channels.size();
-        hipLaunchKernelGGL(k_iota_topn, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
-                           0, s->stream, d_perm, total_rows);
-        TG_HIP_CHECK(hipGetLastError());
-        if (!k) return TG_OK;
-        std::vector<uint64_t*> kf(k, nullptr), nf(k, nullptr);
-        for (size_t j = 0; j < k; j++) {
-            int32_t ch = j < np ? partition_channels[j] : sort_channels[j - np];
-            int32_t desc = j < np ? 0 : (sort_desc[j - np] != 0);
-            WIN_TRY(ws.alloc(&kf[j], total_rows * 8));
-            bool nullable = false;
-            for (auto& pg : pages) nullable |= pg.n && pg.blocks[ch].valid;
-            if (nullable) WIN_TRY(ws.alloc(&nf[j], total_rows * 8));
-            for (size_t p = 0; p < pages.size(); p++) {
-                const DevBlock& b = pages[p].blocks[ch];
-                if (!pages[p].n) continue;
-                hipLaunchKernelGGL(k_topn_keys, dim3(tg_grid_for(pages[p].n)),
-                                   dim3(TG_BLOCK), 0, s->stream, b.data, b.valid,
-                                   (int32_t)b.type, desc, pages[p].n,
-                                   kf[j] + page_base[p]);
-                TG_HIP_CHECK(hipGetLastError());
-                if (!nullable) continue;
-                hipLaunchKernelGGL(k_topn_null_keys, dim3(tg_grid_for(pages[p].n)),
-                                   dim3(TG_BLOCK), 0, s->stream, b.valid,
-                                   desc, pages[p].n, nf[j] + page_base[p]);
-                TG_HIP_CHECK(hipGetLastError());
-            }
-            host_keys->push_back(WinKey{kf[j], nf[j]});
-        }
-        uint64_t* d_keys = nullptr;
-        WIN_TRY(ws.alloc(&d_keys, total_rows * 8));
-        for (int j = (int)k - 1; j >= 0; j--) {
-            hipLaunchKernelGGL(k_gather_u64_by_perm, dim3(tg_grid_for(total_rows)),
-                               dim3(TG_BLOCK), 0, s->stream, kf[j], d_perm,
-                               total_rows, d_keys);
-            TG_HIP_CHECK(hipGetLastError());
-            WIN_TRY(run_sort_pairs(s, d_keys, d_perm, total_rows));
-            if (!nf[j]) continue;
-            /* the channel's major order: NULL or not, one stable 1-bit pass */
-            hipLaunchKernelGGL(k_gather_u64_by_perm, dim3(tg_grid_for(total_rows)),
-                               dim3(TG_BLOCK), 0, s->stream, nf[j], d_perm,
-                               total_rows, d_keys);
-            TG_HIP_CHECK(hipGetLastError());
-            WIN_TRY(run_sort_pairs_bits(s, d_keys, d_perm, total_rows, 1));
-        }
         return TG_OK;
     }
 
     /* aggregate input of channel ch in sorted order */
-    tg_status gather_input(WinScratch& ws, const std::vector<int64_t>& page_base,
+    tg_status gather_input(PoolScratch& ws, const std::vector<int64_t>& page_base,
                            const int64_t* d_perm, int32_t ch, int64_t** vals_out,
                            int64_t** nonnull_out)
     {
         int64_t *vals = nullptr, *nonnull = nullptr;
-        WIN_TRY(ws.alloc(&vals, total_rows * 8));
-        WIN_TRY(ws.alloc(&nonnull, total_rows * 8));
+        TG_TRY(ws.alloc(&vals, total_rows * 8));
+        TG_TRY(ws.alloc(&nonnull, total_rows * 8));
         dim3 grid(tg_grid_for(total_rows)), block(TG_BLOCK);
         for (size_t p = 0; p < pages.size(); p++) {
             const DevBlock& sb = pages[p].blocks[ch];
             int64_t pn = pages[p].n;
             if (!pn) continue;
-            switch (sb.elem_size()) {
-                case 8: hipLaunchKernelGGL(k_win_gather_input<int64_t>, grid, block, 0, s->stream,
-                            (const int64_t*)sb.data, sb.valid, d_perm, total_rows, page_base[p],
-                            pn, vals, nonnull); break;
-                case 4: hipLaunchKernelGGL(k_win_gather_input<int32_t>, grid, block, 0, s->stream,
-                            (const int32_t*)sb.data, sb.valid, d_perm, total_rows, page_base[p],
-                            pn, vals, nonnull); break;
-                case 2: hipLaunchKernelGGL(k_win_gather_input<int16_t>, grid, block, 0, s->stream,
-                            (const int16_t*)sb.data, sb.valid, d_perm, total_rows, page_base[p],
-                            pn, vals, nonnull); break;
-                default: hipLaunchKernelGGL(k_win_gather_input<int8_t>, grid, block, 0, s->stream,
-                            (const int8_t*)sb.data, sb.valid, d_perm, total_rows, page_base[p],
-                            pn, vals, nonnull); break;
-            }
+            tg_dispatch_width(sb.elem_size(), [&](auto t) {
+                using T = decltype(t);
+                hipLaunchKernelGGL(k_win_gather_input<T>, grid, block, 0, s->stream,
+                                   (const T*)sb.data, sb.valid, d_perm, total_rows,
+                                   page_base[p], pn, vals, nonnull);
+            });
             TG_HIP_CHECK(hipGetLastError());
         }
         *vals_out = vals;
@@ -665,50 +549,7 @@ struct WindowOp : tg_operator {
         return TG_OK;
     }
 
-    /* every input channel through the final permutation, validity included */
-    tg_status gather_payload(const std::vector<int64_t>& page_base, const int64_t* d_perm,
-                             DevPage* outp)
-    {
-        int64_t take = total_rows;
-        for (size_t c = 0; c < types.size(); c++) {
-            outp->blocks.emplace_back();
-            DevBlock& b = outp->blocks.back();
-            b.type = types[c];
-            b.n = take;
-            TG_POOL_ALLOC(s, &b.data, take * b.elem_size());
-            bool nullable = false;
-            for (auto& pg : pages) nullable |= pg.n && pg.blocks[c].valid;
-            if (nullable) {
-                int64_t words = (take + 63) / 64;
-                TG_POOL_ALLOC(s, &b.valid, words * 8);
-                TG_HIP_CHECK(hipMemsetAsync(b.valid, 0xFF, words * 8, s->stream));
-            }
-            for (size_t p = 0; p < pages.size(); p++) {
-                const DevBlock& sb = pages[p].blocks[c];
-                int64_t pn = pages[p].n;
-                if (!pn) continue;
-                dim3 grid(tg_grid_for(take)), block(TG_BLOCK);
-                switch (b.elem_size()) {
-                    case 8: hipLaunchKernelGGL(k_topn_gather<int64_t>, grid, block, 0, s->stream,
-                                (const int64_t*)sb.data, sb.valid, d_perm, take, page_base[p], pn,
-                                (int64_t*)b.data, b.valid); break;
-                    case 4: hipLaunchKernelGGL(k_topn_gather<int32_t>, grid, block, 0, s->stream,
-                                (const int32_t*)sb.data, sb.valid, d_perm, take, page_base[p], pn,
-                                (int32_t*)b.data, b.valid); break;
-                    case 2: hipLaunchKernelGGL(k_topn_gather<int16_t>, grid, block, 0, s->stream,
-                                (const int16_t*)sb.data, sb.valid, d_perm, take, page_base[p], pn,
-                                (int16_t*)b.data, b.valid); break;
-                    default: hipLaunchKernelGGL(k_topn_gather<int8_t>, grid, block, 0, s->stream,
-                                (const int8_t*)sb.data, sb.valid, d_perm, take, page_base[p], pn,
-                                (int8_t*)b.data, b.valid); break;
-                }
-                TG_HIP_CHECK(hipGetLastError());
-            }
-        }
-        return TG_OK;
-    }
-
-    tg_status emit_into(WinScratch& ws, DevPage* outp)
+    tg_status emit_into(PoolScratch& ws, DevPage* outp)
     {
         const int64_t n = total_rows;
         std::vector<int64_t> page_base(pages.size() + 1, 0);
@@ -716,15 +557,21 @@ struct WindowOp : tg_operator {
             page_base[p + 1] = page_base[p] + pages[p].n;
 
         int64_t* d_perm = nullptr;
-        WIN_TRY(ws.alloc(&d_perm, n * 8));
+        TG_TRY(ws.alloc(&d_perm, n * 8));
+        /* partition channels first (ASC NULLS LAST), then the sort channels;
+         * the key images stay alive in the scratch for the boundary kernel */
+        std::vector<std::pair<int32_t, int32_t>> keys;
+        for (int32_t ch : partition_channels) keys.emplace_back(ch, 0);
+        for (size_t j = 0; j < sort_channels.size(); j++)
+            keys.emplace_back(sort_channels[j], sort_desc[j] != 0);
         std::vector<WinKey> host_keys;
-        WIN_TRY(sort_rows(ws, page_base, d_perm, &host_keys));
+        TG_TRY(order_pages(s, ws, pages, n, keys, d_perm, &host_keys));
 
         /* partition-start and peer-start bits of every sorted position */
         uint8_t* d_flags = nullptr;
         WinKey* d_keytab = nullptr;
-        WIN_TRY(ws.alloc(&d_flags, n));
-        WIN_TRY(ws.alloc(&d_keytab, (int64_t)(host_keys.size() * sizeof(WinKey))));
+        TG_TRY(ws.alloc(&d_flags, n));
+        TG_TRY(ws.alloc(&d_keytab, (int64_t)(host_keys.size() * sizeof(WinKey))));
         if (!host_keys.empty()) {
             TG_HIP_CHECK(hipMemcpyAsync(d_keytab, host_keys.data(),
                                         host_keys.size() * sizeof(WinKey),
@@ -737,8 +584,8 @@ struct WindowOp : tg_operator {
                            d_flags);
         TG_HIP_CHECK(hipGetLastError());
 
-        outp->n = n;
-        WIN_TRY(gather_payload(page_base, d_perm, outp));
+        /* every input channel through the final permutation */
+        TG_TRY(gather_pages(s, pages, types, d_perm, n, outp));
 
         /* intermediates shared by the specs, each computed at most once */
         int64_t* d_rownum = nullptr;
@@ -763,23 +610,23 @@ struct WindowOp : tg_operator {
         };
         auto rownum = [&]() -> tg_status {
             if (d_rownum) return TG_OK;
-            WIN_TRY(ws.alloc(&d_rownum, n * 8));
+            TG_TRY(ws.alloc(&d_rownum, n * 8));
             return scan(WSRC_ONE, WOP_ADD, WFLAG_PARTITION, 0, nullptr, nullptr, 0, d_rownum);
         };
         /* index of the last row of the peer group (RANGE) or partition */
         auto frame_end = [&](int32_t frame) -> tg_status {
             if (frame == TG_WIN_FRAME_ROWS || d_end[frame]) return TG_OK;
-            WIN_TRY(ws.alloc(&d_end[frame], n * 8));
+            TG_TRY(ws.alloc(&d_end[frame], n * 8));
             int32_t mask = frame == TG_WIN_FRAME_RANGE ? WFLAG_PEER : WFLAG_PARTITION;
             return scan(WSRC_INDEX, WOP_MAX, mask, 0, nullptr, nullptr, 1, d_end[frame]);
         };
         auto input = [&](int32_t ch) -> tg_status {
             if (inputs.count(ch)) return TG_OK;
             Input in{nullptr, nullptr, nullptr};
-            WIN_TRY(gather_input(ws, page_base, d_perm, ch, &in.vals, &in.nonnull));
-            WIN_TRY(ws.alloc(&in.count, n * 8));
-            WIN_TRY(scan(WSRC_ARRAY, WOP_ADD, WFLAG_PARTITION, 0, in.nonnull, nullptr, 0,
-                         in.count));
+            TG_TRY(gather_input(ws, page_base, d_perm, ch, &in.vals, &in.nonnull));
+            TG_TRY(ws.alloc(&in.count, n * 8));
+            TG_TRY(scan(WSRC_ARRAY, WOP_ADD, WFLAG_PARTITION, 0, in.nonnull, nullptr, 0,
+                        in.count));
             inputs[ch] = in;
             return TG_OK;
         };
@@ -800,11 +647,11 @@ struct WindowOp : tg_operator {
             /* ROWS_BETWEEN clamps at the partition end */
             int32_t endf = sp.frame == TG_WIN_FRAME_ROWS_BETWEEN ? (int32_t)TG_WIN_FRAME_PARTITION
                                                                  : sp.frame;
-            WIN_TRY(rownum());
-            WIN_TRY(frame_end(endf));
+            TG_TRY(rownum());
+            TG_TRY(frame_end(endf));
             Bounds b{nullptr, nullptr};
-            WIN_TRY(ws.alloc(&b.lo, n * 8));
-            WIN_TRY(ws.alloc(&b.hi, n * 8));
+            TG_TRY(ws.alloc(&b.lo, n * 8));
+            TG_TRY(ws.alloc(&b.hi, n * 8));
             hipLaunchKernelGGL(k_win_bounds, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0, s->stream,
                                sp.frame, sp.frame_start, sp.frame_end,
                                (const int64_t*)d_rownum, (const int64_t*)d_end[endf], n,
@@ -823,8 +670,8 @@ struct WindowOp : tg_operator {
             }
             const Input& in = inputs[ch];
             int64_t* r = nullptr;
-            WIN_TRY(ws.alloc(&r, n * 8));
-            WIN_TRY(scan(WSRC_NEUTRAL, op, WFLAG_PARTITION, 0, in.vals, in.nonnull, reverse, r));
+            TG_TRY(ws.alloc(&r, n * 8));
+            TG_TRY(scan(WSRC_NEUTRAL, op, WFLAG_PARTITION, 0, in.vals, in.nonnull, reverse, r));
             runnings[key] = r;
             *got = r;
             return TG_OK;
@@ -842,16 +689,16 @@ struct WindowOp : tg_operator {
                 /* the cells in sorted order are the payload channel itself */
                 const DevBlock& src = outp->blocks[sp.input_channel];
                 Bounds fb{nullptr, nullptr};
-                if (sp.fn == TG_WIN_LAG) WIN_TRY(rownum());
-                else if (sp.fn == TG_WIN_LEAD) WIN_TRY(frame_end(TG_WIN_FRAME_PARTITION));
-                else WIN_TRY(frame_bounds(sp, &fb));
-                WIN_TRY(launch_value(sp.fn - TG_WIN_LAG, sp.offset, src, fb.lo, fb.hi, d_rownum,
-                                     d_end[TG_WIN_FRAME_PARTITION], b));
+                if (sp.fn == TG_WIN_LAG) TG_TRY(rownum());
+                else if (sp.fn == TG_WIN_LEAD) TG_TRY(frame_end(TG_WIN_FRAME_PARTITION));
+                else TG_TRY(frame_bounds(sp, &fb));
+                TG_TRY(launch_value(sp.fn - TG_WIN_LAG, sp.offset, src, fb.lo, fb.hi, d_rownum,
+                                    d_end[TG_WIN_FRAME_PARTITION], b));
                 continue;
             }
             if (sp.frame == TG_WIN_FRAME_ROWS_BETWEEN) {
                 Bounds fb{nullptr, nullptr};
-                WIN_TRY(frame_bounds(sp, &fb));
+                TG_TRY(frame_bounds(sp, &fb));
                 dim3 grid(tg_grid_for(n)), block(TG_BLOCK);
                 if (sp.fn == TG_WIN_COUNT_STAR) {
                     hipLaunchKernelGGL(k_win_frame_emit, grid, block, 0, s->stream,
@@ -862,7 +709,7 @@ struct WindowOp : tg_operator {
                     TG_HIP_CHECK(hipGetLastError());
                     continue;
                 }
-                WIN_TRY(input(sp.input_channel));
+                TG_TRY(input(sp.input_channel));
                 const Input in = inputs[sp.input_channel];
                 int32_t op = sp.fn == TG_WIN_MIN_I64 ? WOP_MIN
                            : sp.fn == TG_WIN_MAX_I64 ? WOP_MAX : WOP_ADD;
@@ -875,7 +722,7 @@ struct WindowOp : tg_operator {
                     const int64_t* S = in.count;
                     if (sp.fn != TG_WIN_COUNT_COL) {
                         int64_t* r = nullptr;
-                        WIN_TRY(running(sp.input_channel, op, mode == WFE_AT_LO, &r));
+                        TG_TRY(running(sp.input_channel, op, mode == WFE_AT_LO, &r));
                         S = r;
                     }
                     hipLaunchKernelGGL(k_win_frame_emit, grid, block, 0, s->stream, mode, S,
@@ -888,7 +735,7 @@ struct WindowOp : tg_operator {
                 /* sliding min / max: one launch per level of the widest frame */
                 int32_t levels = window_levels(sp.frame_start, sp.frame_end, n);
                 int64_t* T[2] = {nullptr, nullptr};
-                for (int t = 0; t < 2 && t < levels - 1; t++) WIN_TRY(ws.alloc(&T[t], n * 8));
+                for (int t = 0; t < 2 && t < levels - 1; t++) TG_TRY(ws.alloc(&T[t], n * 8));
                 for (int32_t k = 0; k < levels; k++) {
                     const int64_t* src = k ? T[(k - 1) & 1] : in.vals;
                     hipLaunchKernelGGL(k_win_level, grid, block, 0, s->stream, k, op, src,
@@ -902,41 +749,41 @@ struct WindowOp : tg_operator {
                 continue;
             }
             if (sp.fn == TG_WIN_RANK) {
-                WIN_TRY(rownum());
-                WIN_TRY(scan(WSRC_MASKED, WOP_MAX, WFLAG_PARTITION, WFLAG_PEER, d_rownum,
-                             nullptr, 0, out));
+                TG_TRY(rownum());
+                TG_TRY(scan(WSRC_MASKED, WOP_MAX, WFLAG_PARTITION, WFLAG_PEER, d_rownum,
+                            nullptr, 0, out));
                 continue;
             }
             if (sp.fn == TG_WIN_DENSE_RANK) {
-                WIN_TRY(scan(WSRC_FLAG, WOP_ADD, WFLAG_PARTITION, WFLAG_PEER, nullptr,
-                             nullptr, 0, out));
+                TG_TRY(scan(WSRC_FLAG, WOP_ADD, WFLAG_PARTITION, WFLAG_PEER, nullptr,
+                            nullptr, 0, out));
                 continue;
             }
             /* the ROWS-frame result, then the frame's gather */
             const int64_t* rows_result = nullptr;
             const int64_t* count = nullptr;
             if (sp.fn == TG_WIN_ROW_NUMBER || sp.fn == TG_WIN_COUNT_STAR) {
-                WIN_TRY(rownum());
+                TG_TRY(rownum());
                 rows_result = d_rownum;
             }
             else {
-                WIN_TRY(input(sp.input_channel));
+                TG_TRY(input(sp.input_channel));
                 const Input& in = inputs[sp.input_channel];
                 if (sp.fn == TG_WIN_COUNT_COL) rows_result = in.count;
                 else {
                     int32_t op = sp.fn == TG_WIN_SUM_I64 ? WOP_ADD
                                : sp.fn == TG_WIN_MIN_I64 ? WOP_MIN : WOP_MAX;
                     int64_t* r = nullptr;
-                    WIN_TRY(ws.alloc(&r, n * 8));
-                    WIN_TRY(scan(WSRC_NEUTRAL, op, WFLAG_PARTITION, 0, in.vals, in.nonnull,
-                                 0, r));
+                    TG_TRY(ws.alloc(&r, n * 8));
+                    TG_TRY(scan(WSRC_NEUTRAL, op, WFLAG_PARTITION, 0, in.vals, in.nonnull,
+                                0, r));
                     rows_result = r;
                     count = in.count;
                 }
             }
             /* row_number has no frame: its frame field is 0 by contract */
             int32_t frame = sp.fn == TG_WIN_ROW_NUMBER ? TG_WIN_FRAME_ROWS : sp.frame;
-            WIN_TRY(frame_end(frame));
+            TG_TRY(frame_end(frame));
             hipLaunchKernelGGL(k_win_emit, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0, s->stream,
                                rows_result, count, (const int64_t*)d_end[frame], n, out,
                                b.valid);
@@ -952,7 +799,7 @@ struct WindowOp : tg_operator {
             DevPage outp;
             tg_status st;
             {
-                WinScratch ws(s);
+                PoolScratch ws(s);
                 st = emit_into(ws, &outp);
             }   /* the scratch is back in the pool, the stream drained */
             if (st != TG_OK) {

@@ -1,14 +1,13 @@
-/* sort_keys.h — sort-key images and permutation gathers shared by the TopN
- * operator (ops_topn.hip) and the Window operator (ops_window.hip).
- *
- * Both order rows by stable radix passes over one u64 image per key channel
- * (run_sort_pairs, least-significant channel first) and gather the payload
- * through the resulting permutation. The kernels are `static`: every operator
- * file that includes this header gets its own copy, so the two translation
- * units do not collide at link time.
+/* sort_keys.h — the ordering path shared by the TopN operator (ops_topn.hip)
+ * and the Window operator (ops_window.hip): the sortable image of a key cell,
+ * and the declarations of the host functions in sort.hip that check an input
+ * page, order the accumulated pages and gather them through an index array.
+ * The kernels behind them are defined once, in sort.hip.
  */
 #pragma once
 #include "common.h"
+#include "operators.h"
+#include <utility>
 
 /* order-preserving map to an unsigned "ascending sortable" key space:
  * integers: flip the sign bit; doubles: IEEE total-order trick after
@@ -38,68 +37,30 @@ __device__ static inline uint64_t topn_sortable(const void* data, int32_t type, 
     }
 }
 
-static __global__ void k_topn_keys(const void* __restrict__ data,
-                                   const uint64_t* __restrict__ valid, int32_t type,
-                                   int32_t desc, int64_t n, uint64_t* __restrict__ out)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        bool isnull = valid && !((valid[i >> 6] >> (i & 63)) & 1);
-        uint64_t key;
-        if (isnull) key = 0ull;   /* placed by the null pass */
-        else {
-            key = topn_sortable(data, type, i);
-            if (desc) key = ~key;
-        }
-        out[i] = key;
-    }
-}
+/* key images of one ordering channel, indexed by flat input row */
+struct SortKeyImages {
+    const uint64_t* kf;   /* topn_sortable image (0 where NULL) */
+    const uint64_t* nf;   /* null-pass bit; nullptr when the channel has no NULLs */
+};
 
-/* 1-bit key of the null pass: ASC nulls last (1), DESC nulls first (0) */
-static __global__ void k_topn_null_keys(const uint64_t* __restrict__ valid, int32_t desc,
-                                        int64_t n, uint64_t* __restrict__ out)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        bool isnull = valid && !((valid[i >> 6] >> (i & 63)) & 1);
-        out[i] = (isnull != (desc != 0)) ? 1ull : 0ull;
-    }
-}
+/* the page has at least types.size() channels, none VARCHAR, each as wide as
+ * declared; `op` names the operator in the error text */
+tg_status check_fixed_width_page(const char* op, const tg_page* page,
+                                 const std::vector<tg_type>& types);
 
-/* output gather of one source page: output slot o takes flat row idx[o] when
- * it lies in this page ([base, base + n)); a NULL source cell clears the
- * output's validity bit */
-template <typename T>
-__global__ void k_topn_gather(const T* __restrict__ src, const uint64_t* __restrict__ src_valid,
-                              const int64_t* __restrict__ idx, int64_t take,
-                              int64_t base, int64_t n, T* __restrict__ out,
-                              uint64_t* __restrict__ out_valid)
-{
-    int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; o < take; o += stride) {
-        int64_t r = idx[o] - base;
-        if (r < 0 || r >= n) continue;
-        out[o] = src[r];
-        if (src_valid && !((src_valid[r >> 6] >> (r & 63)) & 1))
-            atomicAnd((unsigned long long*)&out_valid[o >> 6], ~(1ull << (o & 63)));
-    }
-}
+/* order the total_rows rows of `pages` by (channel, desc) keys, most
+ * significant first, into d_perm[total_rows] (flat row indices; ASC = nulls
+ * last, DESC = nulls first; whole-key ties keep input order). Temporaries
+ * come from `ps`; with `images` the per-key images are handed back, alive as
+ * long as `ps`. */
+tg_status order_pages(tg_session* s, PoolScratch& ps, const std::vector<DevPage>& pages,
+                      int64_t total_rows,
+                      const std::vector<std::pair<int32_t, int32_t>>& keys,
+                      int64_t* d_perm, std::vector<SortKeyImages>* images);
 
-static __global__ void k_gather_u64_by_perm(const uint64_t* __restrict__ kf,
-                                            const int64_t* __restrict__ perm, int64_t n,
-                                            uint64_t* __restrict__ out)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) out[i] = kf[perm[i]];
-}
-
-static __global__ void k_iota_topn(int64_t* v, int64_t n)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) v[i] = i;
-}
+/* gather channels [0, types.size()) of `pages` through the flat row indices
+ * d_idx[take] into outp, validity included. Asynchronous on the session
+ * stream; on error outp holds what was allocated, for tg_free_page. */
+tg_status gather_pages(tg_session* s, const std::vector<DevPage>& pages,
+                       const std::vector<tg_type>& types, const int64_t* d_idx,
+                       int64_t take, DevPage* outp);

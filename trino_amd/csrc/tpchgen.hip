@@ -10,6 +10,7 @@
  * then sequential generation, rows written at the scanned offsets.
  */
 #include "common.h"
+#include "operators.h"   /* run_sort_keys_u32, run_sort_pairs_bits */
 
 #define TPCH_HD __host__ __device__
 #include "../../oracle/tpch_core.h"
@@ -608,9 +609,6 @@ __global__ void k_var_like(const uint8_t* __restrict__ bytes,
  * (evaluate once per dictionary entry) applied to the text pool. The
  * per-row byte scan (like_match) measured 26.4 ms for Q13's 150M x ~49 B
  * comments at SF100; see profiles/ for the indexed number. */
-tg_status run_sort_keys_u32(tg_session* s, uint32_t* d_keys, int64_t n);
-tg_status run_sort_pairs_bits(tg_session* s, uint64_t* d_keys, int64_t* d_vals,
-                              int64_t n, int bits);
 
 struct LikeIdx {
     const uint32_t* occ[LIKE_MAX_SEGS];
