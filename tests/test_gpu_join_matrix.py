@@ -914,10 +914,9 @@ def _words(idx):
     return [b"k" * (int(i) % 5) + str(int(i) // 5).encode() for i in idx]
 
 
-@pytest.mark.parametrize("outer", [False, True], ids=["inner", "outer"])
-def test_multi_page_build_varchar(sess, ops, outer):
-    """the same with a VARCHAR key and a VARCHAR output column: concat_varchar
-    and k_off_rebase"""
+def multi_page_varchar_case(sess, ops, outer):
+    """the multi-page build with a VARCHAR key and a VARCHAR output column,
+    checked against ref_join"""
     nb = sum(MULTI_PAGE_SIZES)
     r = rng(4)
     g = r.permutation(np.repeat(np.arange(nb), (np.arange(nb) % 3) + 1)[:nb])
@@ -933,7 +932,14 @@ def test_multi_page_build_varchar(sess, ops, outer):
     probe = [nullable("str", _words(pg), np.arange(m) % 31 == 7, POISON_S),
              Col("i64", np.arange(m))]
     bpages = split_pages(build, MULTI_PAGE_SIZES, MULTI_PAGE_BITMAPS)
-    join_case(sess, ops, bpages, [0], [0, 1, 2], [probe], [0], [0, 1], outer)
+    return join_case(sess, ops, bpages, [0], [0, 1, 2], [probe], [0], [0, 1], outer)
+
+
+@pytest.mark.parametrize("outer", [False, True], ids=["inner", "outer"])
+def test_multi_page_build_varchar(sess, ops, outer):
+    """the same with a VARCHAR key and a VARCHAR output column: concat_varchar
+    and k_off_rebase"""
+    multi_page_varchar_case(sess, ops, outer)
 
 
 # --------------------------------------------------------------------------

@@ -1,11 +1,13 @@
-"""Pool balance of the ordering path: TopN (both paths), Window and
-tg_dedup_i64 return every temporary to the session pool.
+"""Pool balance of the ordering path and of the hash join: TopN (both paths),
+Window, tg_dedup_i64 and the join's build, probe, lookup-outer and semi
+operators return every temporary to the session pool.
 
 Each case records live = total - cached pool bytes (trino_amd.session_memory)
 before the operator exists, runs it to completion, closes it and expects
 exactly that value again; `live` and not `total`, because the pool may evict
 cached buffers. Each case also compares the output with a reference
-(np.lexsort, ref_window_ex_vec of test_window_frames_reference, np.unique), so
+(np.lexsort, ref_window_ex_vec of test_window_frames_reference, np.unique,
+ref_join / ref_semi / ref_unmatched through the join matrices' runners), so
 none passes by doing nothing. The shapes are the smallest at which every
 temporary of the path is taken. The failure paths need an allocation failure
 and are not run here.
@@ -13,8 +15,11 @@ and are not run here.
 import numpy as np
 import pytest
 
+import test_gpu_join_matrix as jm
 from test_gpu_filter_matrix import Col, POISON, unpack_bits
+from test_gpu_join_matrix import partitioned  # noqa: F401  (fixture)
 from test_gpu_ordering_matrix import HOST_ROWS, TOPN_DEVICE_ROWS, run_topn
+from test_gpu_outer_join_matrix import single_key_outer
 from test_gpu_text_distinct_matrix import run_dedup
 from test_gpu_window_frames_matrix import check_window_ex
 from test_gpu_window_matrix import WSCAN_ONE_WAVE
@@ -101,3 +106,84 @@ def test_dedup(sess, ops):
     m, got = run_dedup(sess, keys, 64)
     assert live(sess) == start
     assert m == len(exp) and np.array_equal(got, exp)
+
+
+# --------------------------------------------------------------------------
+# hash join: build, probe paths, lookup-outer and semi join. Each case is a
+# checked case of the join matrices, which compare every column against
+# ref_join, ref_semi or ref_unmatched and close the operators and the bridge.
+# --------------------------------------------------------------------------
+@pytest.mark.parametrize("outer", [False, True], ids=["inner", "outer"])
+def test_join_csr_classic(sess, ops, outer):
+    """nullable key bitmap, the CSR temporaries, count / scan / fill and the
+    gathers (with NULL positions when probe-outer)"""
+    start = live(sess)
+    jm.single_key_case(sess, ops, "nulls", 1000, jm.SMALL_M, outer)
+    assert live(sess) == start
+
+
+def test_join_multi_page_varchar(sess, ops):
+    """VARCHAR concatenation, the generic build key columns and the probe-side
+    key column array"""
+    start = live(sess)
+    jm.multi_page_varchar_case(sess, ops, False)
+    assert live(sess) == start
+
+
+def test_join_partitioned_overflow_retry(sess, ops, partitioned):  # noqa: F811
+    """the six partition temporaries, the early release of the first-try match
+    lists and the match sort"""
+    build, probe = jm.bigint_tables(*jm.overflow_inputs())
+    start = live(sess)
+    got = jm.join_case(sess, ops, [build], [0], [0, 1, 2], [probe], [0], [0, 1],
+                       False, order="list")
+    assert live(sess) == start
+    assert len(got[0]) == jm.OVERFLOW_N * jm.OVERFLOW_N
+
+
+def test_join_full_and_lookup_outer(sess, ops):
+    """the visited bitmap, the unmatched-row emission and its all-NULL columns"""
+    start = live(sess)
+    assert single_key_outer(sess, ops, "dups", 1000, jm.SMALL_M, 3) is not None
+    assert live(sess) == start
+
+
+def test_semi_join_set_source(sess, ops):
+    """set builder over a dense key range: the bitmap and no index"""
+    bk, bnull = jm.set_shapes()["nulls_inside_run"]
+    lo, hi = int(bk.min()), int(bk.max())
+    pk = np.arange(lo - 70, hi + 71, dtype=np.int64)
+    build = [jm.nullable("i64", bk, bnull, lo - 3)]
+    probe = [jm.nullable("i64", pk, np.arange(len(pk)) % 13 == 6, lo)]
+    start = live(sess)
+    jm.semi_case(sess, ops, [build], 0, [probe], 0, source="set")
+    assert live(sess) == start
+
+
+def test_semi_join_generic_key(sess, ops):
+    """a DOUBLE key takes the generic path and the probe-side key column array"""
+    build, probe = jm.semi_tables("double", "dups", True)
+    start = live(sess)
+    jm.semi_case(sess, ops, [build], 0, [probe], 0, source="hash")
+    assert live(sess) == start
+
+
+def test_join_requested_bitmap(sess, ops):
+    """a dynamic-filter bitmap requested beside the index; these sparse keys
+    span more than 2^33, so only the key-range pass runs"""
+    start = live(sess)
+    jm.single_key_case(sess, ops, "unique", 1000, jm.SMALL_M, False,
+                       request_bitmap=True)
+    assert live(sess) == start
+
+
+def test_join_requested_bitmap_dense(sess, ops):
+    """the same over a dense key range, where the bitmap is built"""
+    r = np.random.default_rng(12)
+    bk = r.integers(-300, 900, 1000).astype(np.int64)
+    pk = r.integers(-400, 1000, jm.SMALL_M).astype(np.int64)
+    build, probe = jm.bigint_tables(bk, np.arange(1000) % 50 == 7, pk, None)
+    start = live(sess)
+    jm.join_case(sess, ops, [build], [0], [0, 1, 2], [probe], [0], [0, 1], False,
+                 request_bitmap=True)
+    assert live(sess) == start

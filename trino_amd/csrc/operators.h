@@ -66,6 +66,15 @@ struct PoolScratch {
         *out = (T*)p;
         return TG_OK;
     }
+    /* own a buffer that a callee allocated (make_kcols); null is ignored */
+    void adopt(void* p) { bufs.push_back(p); }
+    /* free one buffer early, after the stream has drained, and forget it */
+    void release(void* p)
+    {
+        (void)hipStreamSynchronize(s->stream);
+        for (void*& q : bufs)
+            if (q == p) { tg_pool_free(s, p); q = bufs.back(); bufs.pop_back(); return; }
+    }
     ~PoolScratch()
     {
         (void)hipStreamSynchronize(s->stream);
@@ -79,6 +88,19 @@ struct PoolScratch {
  * micro-semantics). */
 tg_status tg_upload_page(tg_session* s, const tg_page* in, DevPage* out);
 void tg_free_page(tg_session* s, DevPage* p);
+
+/* a page of one piece of work: its blocks go back to the pool on every path
+ * unless the page was handed on with take(). Declare it before a PoolScratch
+ * whose kernels read the page, so the scratch drains the stream first. */
+struct PageGuard {
+    tg_session* s;
+    DevPage& page;
+    PageGuard(tg_session* s_, DevPage& p) : s(s_), page(p) {}
+    PageGuard(const PageGuard&) = delete;
+    PageGuard& operator=(const PageGuard&) = delete;
+    DevPage&& take() { return std::move(page); }   /* leaves the page empty */
+    ~PageGuard() { tg_free_page(s, &page); }
+};
 
 struct tg_operator {
     tg_session* s = nullptr;

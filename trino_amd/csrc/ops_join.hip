@@ -138,7 +138,14 @@ __device__ static inline bool probe_matches(const JoinTable& t, const ProbeKeys&
 }
 
 struct tg_join_bridge {
-    tg_session* s = nullptr;
+    tg_session* s;
+    /* owner of every device buffer that lives as long as the bridge: the
+     * table arrays of `t`, set_bitmap, kv, d_bkeys, visited and the data,
+     * valid and offsets of build_channels. The fields that point at them stay
+     * plain pointers (JoinTable goes to kernels by value); closing the bridge
+     * frees them all. */
+    PoolScratch own;
+    explicit tg_join_bridge(tg_session* s_) : s(s_), own(s_) {}
     JoinTable t;
     /* dynamic filter source (DynamicFilterSourceOperator /
      * sql/gen/columnar/DynamicPageFilter.java analog): min/max of the
@@ -203,6 +210,26 @@ static tg_status check_probe_keys(const tg_join_bridge* b, const tg_page* page,
             return TG_ERR_INVALID_ARG;
         }
     }
+    return TG_OK;
+}
+
+/* probe-side key context over an uploaded page: the BIGINT key pointers, or
+ * for generic keys a device KColH array that `scratch` owns */
+static tg_status probe_keys_of(tg_session* s, const JoinTable& t, const DevPage& in,
+                               const int32_t* channels, int n_channels,
+                               PoolScratch& scratch, ProbeKeys* pkc)
+{
+    if (t.generic) {
+        KColH* d_pkg = nullptr;
+        tg_status st = make_kcols(s, in, channels, n_channels, &d_pkg);
+        scratch.adopt(d_pkg);     /* also when the copy after its allocation failed */
+        pkc->pkg = d_pkg;
+        return st;
+    }
+    const DevBlock& kb = in.blocks[channels[0]];
+    if (kb.type != TG_BIGINT) { TG_SET_ERR("single join key must be BIGINT (use multi-channel keys otherwise)"); return TG_ERR_UNSUPPORTED; }
+    pkc->pk = (const int64_t*)kb.data;
+    pkc->pvalid = kb.valid;
     return TG_OK;
 }
 
@@ -761,8 +788,9 @@ static tg_status run_scan_counts(tg_session* s, const int32_t* d_counts, int64_t
 {
     int64_t nchunks = (n + JSCAN_CHUNK - 1) / JSCAN_CHUNK;
     if (nchunks < 1) nchunks = 1;
+    PoolScratch scratch(s);
     int64_t* d_cs = nullptr;
-    TG_POOL_ALLOC(s, &d_cs, nchunks * 8);
+    TG_TRY(scratch.alloc(&d_cs, nchunks * 8));
     int swpb = TG_BLOCK / 64;
     hipLaunchKernelGGL(k_scan_chunk_sums, dim3((uint32_t)((nchunks + swpb - 1) / swpb)),
                        dim3(TG_BLOCK), 0, s->stream, d_counts, n, d_cs, nchunks);
@@ -775,7 +803,6 @@ static tg_status run_scan_counts(tg_session* s, const int32_t* d_counts, int64_t
                        dim3(TG_BLOCK), 0, s->stream, d_counts, n, d_cs, d_offsets, nchunks);
     TG_HIP_CHECK(hipGetLastError());
     TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-    tg_pool_free(s, d_cs);
     return TG_OK;
 }
 
@@ -868,7 +895,7 @@ static tg_status bridge_ensure_visited(tg_join_bridge* b)
     if (b->visited) return TG_OK;
     int64_t words = (b->t.n + 63) / 64;
     if (words < 1) words = 1;
-    TG_POOL_ALLOC(b->s, &b->visited, words * 8);
+    TG_TRY(b->own.alloc(&b->visited, words * 8));
     TG_HIP_CHECK(hipMemsetAsync(b->visited, 0, words * 8, b->s->stream));
     return TG_OK;
 }
@@ -896,17 +923,31 @@ __global__ void k_off_rebase(const int32_t* __restrict__ src, int64_t n,
     for (; i < n; i += stride) dst[i] = src[i] + base;
 }
 
+/* A/B on MI355X (Q3 SF100): CSR 98.0 ms/step vs open addressing 110.1 — CSR
+ * default; TG_JOIN_CSR=0 selects the legacy path. Read once per process. */
+static int join_use_csr()
+{
+    static int v = [] { const char* e = getenv("TG_JOIN_CSR"); return e ? atoi(e) : 1; }();
+    return v;
+}
+
 /* ---- build operator ---- */
 struct HashBuilderOp : tg_operator {
     tg_join_bridge* bridge = nullptr;
     bool set_only = false;          /* SetBuilderOperator: bitmap, no index */
     bool range_done_ = false;
+    std::vector<int32_t> key_channels;
+    std::vector<tg_type> types;
+    std::vector<DevPage> pages;     /* PagesIndex */
+    int64_t total_rows = 0;
 
+    /* dynamic filter source: min/max and count of the non-null build keys */
     tg_status compute_key_range()
     {
         JoinTable& t = bridge->t;
+        PoolScratch scratch(s);
         long long* d_mm = nullptr;
-        TG_POOL_ALLOC(s, &d_mm, 3 * 8);
+        TG_TRY(scratch.alloc(&d_mm, 3 * 8));
         long long init[3] = {INT64_MAX, INT64_MIN, 0};
         TG_HIP_CHECK(hipMemcpyAsync(d_mm, init, 24, hipMemcpyHostToDevice, s->stream));
         if (total_rows > 0) {
@@ -918,42 +959,60 @@ struct HashBuilderOp : tg_operator {
         long long mm[3];
         TG_HIP_CHECK(hipMemcpyAsync(mm, d_mm, 24, hipMemcpyDeviceToHost, s->stream));
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-        tg_pool_free(s, d_mm);
         bridge->key_min = mm[0]; bridge->key_max = mm[1]; bridge->key_rows = mm[2];
         range_done_ = true;
         return TG_OK;
     }
-    std::vector<int32_t> key_channels;
-    std::vector<tg_type> types;
-    std::vector<DevPage> pages;     /* PagesIndex */
-    int64_t total_rows = 0;
 
-    /* concatenate one VARCHAR channel across the accumulated pages
-     * (PagesIndex keeps per-page VariableWidthBlocks; the flat build-side
-     * copy rebases each page's offsets onto a single byte array) */
-    tg_status concat_varchar(size_t c, DevBlock* b)
+    /* an all-valid bitmap over the build rows if any page carries one for
+     * channel c, else *out stays null; owned by the bridge */
+    tg_status alloc_valid(size_t c, uint64_t** out)
     {
+        bool anynull = false;
+        for (auto& p : pages)
+            if (!p.blocks.empty() && p.blocks[c].valid) anynull = true;
+        if (!anynull) return TG_OK;
+        int64_t words = (total_rows + 63) / 64;
+        TG_TRY(bridge->own.alloc(out, words * 8));
+        TG_HIP_CHECK(hipMemsetAsync(*out, 0xFF, words * 8, s->stream));
+        return TG_OK;
+    }
+
+    /* null bitmaps land at arbitrary bit offsets: k_bitmap_concat clears bit
+     * (at + i) of dst per null row of the page block, whatever the page sizes */
+    tg_status concat_valid(const DevBlock& pb, int64_t at, uint64_t* dst)
+    {
+        if (!pb.valid) return TG_OK;
+        hipLaunchKernelGGL(k_bitmap_concat, dim3(tg_grid_for(pb.n)), dim3(TG_BLOCK),
+                           0, s->stream, pb.valid, pb.n, at, dst);
+        TG_HIP_CHECK(hipGetLastError());
+        return TG_OK;
+    }
+
+    /* concatenate channel c across the accumulated pages, contiguous by
+     * global build row. VARCHAR (PagesIndex keeps per-page
+     * VariableWidthBlocks): each page's offsets are rebased onto a single
+     * byte array, and a page's byte count is its last offset. */
+    tg_status concat_channel(size_t c, DevBlock* b)
+    {
+        b->type = types[c];
+        b->n = total_rows;
+        const bool var = b->type == TG_VARCHAR;
+        std::vector<int64_t> page_bytes(pages.size());
         int64_t total_bytes = 0;
-        std::vector<int32_t> page_bytes(pages.size());
         for (size_t pi = 0; pi < pages.size(); pi++) {
             const DevBlock& pb = pages[pi].blocks[c];
             int32_t tb = 0;
-            if (pb.n) {
+            if (var && pb.n) {
                 TG_HIP_CHECK(hipMemcpy(&tb, pb.offsets + pb.n, 4,
                                        hipMemcpyDeviceToHost));
             }
-            page_bytes[pi] = tb;
-            total_bytes += tb;
+            page_bytes[pi] = var ? tb : pb.n * b->elem_size();
+            total_bytes += page_bytes[pi];
         }
-        TG_POOL_ALLOC(s, &b->data, total_bytes ? total_bytes : 1);
-        TG_POOL_ALLOC(s, &b->offsets, (total_rows + 1) * 4);
-        bool anynull = false;
-        for (auto& p : pages) anynull |= p.blocks[c].valid != nullptr;
-        if (anynull) {
-            int64_t words = (total_rows + 63) / 64;
-            TG_POOL_ALLOC(s, &b->valid, words * 8);
-            TG_HIP_CHECK(hipMemsetAsync(b->valid, 0xFF, words * 8, s->stream));
-        }
+        TG_TRY(bridge->own.alloc(&b->data, total_bytes));
+        if (var) TG_TRY(bridge->own.alloc(&b->offsets, (total_rows + 1) * 4));
+        TG_TRY(alloc_valid(c, &b->valid));
         int64_t at = 0, byte_at = 0;
         for (size_t pi = 0; pi < pages.size(); pi++) {
             const DevBlock& pb = pages[pi].blocks[c];
@@ -962,36 +1021,191 @@ struct HashBuilderOp : tg_operator {
                                             page_bytes[pi],
                                             hipMemcpyDeviceToDevice, s->stream));
             }
-            if (pb.n) {
+            if (var && pb.n) {
                 hipLaunchKernelGGL(k_off_rebase, dim3(tg_grid_for(pb.n)),
                                    dim3(TG_BLOCK), 0, s->stream,
                                    pb.offsets, pb.n, (int32_t)byte_at,
                                    b->offsets + at);
                 TG_HIP_CHECK(hipGetLastError());
             }
-            if (pb.valid) {
-                hipLaunchKernelGGL(k_bitmap_concat, dim3(tg_grid_for(pb.n)),
-                                   dim3(TG_BLOCK), 0, s->stream, pb.valid, pb.n,
-                                   at, b->valid);
-                TG_HIP_CHECK(hipGetLastError());
-            }
+            TG_TRY(concat_valid(pb, at, b->valid));
             at += pb.n;
             byte_at += page_bytes[pi];
         }
-        int32_t tb32 = (int32_t)total_bytes;
-        TG_HIP_CHECK(hipMemcpyAsync(b->offsets + total_rows, &tb32, 4,
-                                    hipMemcpyHostToDevice, s->stream));
+        if (var) {
+            int32_t tb32 = (int32_t)total_bytes;
+            TG_HIP_CHECK(hipMemcpyAsync(b->offsets + total_rows, &tb32, 4,
+                                        hipMemcpyHostToDevice, s->stream));
+            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        }
+        return TG_OK;
+    }
+
+    /* the table arrays every build has: the flat key copy with its validity
+     * bitmap, and for the legacy open-addressing table its slots and links */
+    tg_status alloc_table()
+    {
+        JoinTable& t = bridge->t;
+        if (!(join_use_csr() && total_rows > 0)) {
+            TG_TRY(bridge->own.alloc(&t.slots, t.capacity * 4));
+            TG_TRY(bridge->own.alloc(&t.links, total_rows * 4));
+        }
+        TG_TRY(bridge->own.alloc(&t.keys, total_rows * 8));
+        return alloc_valid(key_channels[0], &t.key_valid);
+    }
+
+    /* single BIGINT key -> BigintPagesHash-style flat key copy; otherwise the
+     * DefaultPagesHash-style generic channel compare (requires the CSR table;
+     * the legacy open-addressing path stays single-key) */
+    tg_status copy_keys()
+    {
+        JoinTable& t = bridge->t;
+        t.generic = !(key_channels.size() == 1 &&
+                      bridge->build_channels[key_channels[0]].type == TG_BIGINT);
+        t.n_key_ch = (int32_t)key_channels.size();
+        if (t.generic) {
+            if (!join_use_csr()) { TG_SET_ERR("generic join keys require the CSR table"); return TG_ERR_UNSUPPORTED; }
+            DevPage view;   /* non-owning view over the concatenated channels */
+            view.n = total_rows;
+            view.blocks = bridge->build_channels;
+            tg_status st = make_kcols(s, view, key_channels.data(),
+                                      (int)key_channels.size(), &bridge->d_bkeys);
+            bridge->own.adopt(bridge->d_bkeys);
+            t.bkeys = bridge->d_bkeys;
+            return st;
+        }
+        const DevBlock& kb = bridge->build_channels[key_channels[0]];
+        TG_HIP_CHECK(hipMemcpyAsync(t.keys, kb.data, total_rows * 8,
+                                    hipMemcpyDeviceToDevice, s->stream));
+        if (t.key_valid && kb.valid) {
+            TG_HIP_CHECK(hipMemcpyAsync(t.key_valid, kb.valid,
+                                        (total_rows + 63) / 64 * 8,
+                                        hipMemcpyDeviceToDevice, s->stream));
+        }
+        return TG_OK;
+    }
+
+    /* dense-range key membership bitmap (single BIGINT key): the set
+     * builder's whole table, or the dynamic-filter bitmap requested beside
+     * the index. Best effort: a range beyond 2^33 leaves t.set_bitmap null. */
+    tg_status build_key_bitmap()
+    {
+        JoinTable& t = bridge->t;
+        TG_TRY(compute_key_range());
+        int64_t range = bridge->key_rows > 0
+                      ? bridge->key_max - bridge->key_min + 1 : 0;
+        if (range <= 0 || range > (1ll << 33)) return TG_OK;   /* <= 1 GiB bitmap */
+        int64_t words = (range + 63) / 64;
+        uint64_t* bm = nullptr;
+        TG_TRY(bridge->own.alloc(&bm, words * 8));
+        TG_HIP_CHECK(hipMemsetAsync(bm, 0, words * 8, s->stream));
+        hipLaunchKernelGGL(k_set_bits, dim3(tg_grid_for(total_rows)),
+                           dim3(TG_BLOCK), 0, s->stream, t.keys,
+                           t.key_valid, total_rows, bridge->key_min, bm);
+        TG_HIP_CHECK(hipGetLastError());
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        t.set_bitmap = bm;
+        t.set_min = bridge->key_min;
+        t.set_max = bridge->key_max;
+        return TG_OK;
+    }
+
+    /* CSR index: count -> region-local scan -> host scan of the region totals
+     * -> scatter -> per-bucket sort; the temporaries end with this step */
+    tg_status build_csr()
+    {
+        JoinTable& t = bridge->t;
+        PoolScratch scratch(s);
+        t.csr = 1;
+        int64_t region_slots = t.capacity < JREG_SLOTS ? t.capacity : JREG_SLOTS;
+        int64_t nreg = t.capacity / region_slots;
+        TG_TRY(bridge->own.alloc(&t.bucket_off, (t.capacity + 1) * 4));
+        TG_TRY(bridge->own.alloc(&t.csr_rows, total_rows * 4));
+        uint32_t* d_slot_of = nullptr;
+        int32_t* d_cnt = nullptr;       /* per-slot counts, then cursors */
+        int32_t* d_rtotal = nullptr;
+        int32_t* d_rbase = nullptr;
+        TG_TRY(scratch.alloc(&d_slot_of, total_rows * 4));
+        TG_TRY(scratch.alloc(&d_cnt, t.capacity * 4));
+        TG_TRY(scratch.alloc(&d_rtotal, nreg * 4));
+        TG_TRY(scratch.alloc(&d_rbase, nreg * 4));
+        TG_HIP_CHECK(hipMemsetAsync(d_cnt, 0, t.capacity * 4, s->stream));
+        hipLaunchKernelGGL(k_jc_count, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
+                           0, s->stream, t, d_slot_of, d_cnt);
+        TG_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_jc_local_off, dim3((uint32_t)nreg), dim3(TG_BLOCK),
+                           0, s->stream, d_cnt, t.bucket_off, d_rtotal,
+                           nreg, region_slots);
+        TG_HIP_CHECK(hipGetLastError());
+        std::vector<int32_t> rt(nreg), rb(nreg);
+        TG_HIP_CHECK(hipMemcpyAsync(rt.data(), d_rtotal, nreg * 4,
+                                    hipMemcpyDeviceToHost, s->stream));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        int32_t run = 0;
+        for (int64_t r = 0; r < nreg; r++) { rb[r] = run; run += rt[r]; }
+        int32_t total_indexed = run;    /* == total_rows minus null keys */
+        t.has_null_key = (int64_t)total_indexed < total_rows ? 1 : 0;
+        TG_HIP_CHECK(hipMemcpyAsync(d_rbase, rb.data(), nreg * 4,
+                                    hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(k_jc_addbase, dim3(tg_grid_for(t.capacity)), dim3(TG_BLOCK),
+                           0, s->stream, t.bucket_off, t.capacity, d_rbase,
+                           region_slots);
+        TG_HIP_CHECK(hipGetLastError());
+        TG_HIP_CHECK(hipMemcpyAsync(t.bucket_off + t.capacity, &total_indexed, 4,
+                                    hipMemcpyHostToDevice, s->stream));
+        TG_HIP_CHECK(hipMemcpyAsync(d_cnt, t.bucket_off, t.capacity * 4,
+                                    hipMemcpyDeviceToDevice, s->stream));
+        hipLaunchKernelGGL(k_jc_scatter, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
+                           0, s->stream, t, d_slot_of, d_cnt);
+        TG_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_jc_sort, dim3(tg_grid_for(t.capacity)), dim3(TG_BLOCK),
+                           0, s->stream, t);
+        TG_HIP_CHECK(hipGetLastError());
+        if (!t.generic) {
+            TG_TRY(bridge->own.alloc(&t.csr_keys, total_rows * 8));
+            hipLaunchKernelGGL(k_csr_keys, dim3(tg_grid_for(total_rows)),
+                               dim3(TG_BLOCK), 0, s->stream, t, t.csr_keys);
+            TG_HIP_CHECK(hipGetLastError());
+        }
+        /* A/B on MI355X (Q3 SF100): the 512 MB kv array RAISED probe
+         * time (43.1 vs 39.7 ms per 10 launches) — the CSR arrays it
+         * replaces are smaller and L2-cache better. Kept behind
+         * TG_JOIN_KV=1 for small-table workloads. */
+        static int use_kv = [] { const char* e = getenv("TG_JOIN_KV"); return e ? atoi(e) : 0; }();
+        if (!t.generic && use_kv) {
+            SlotKV* d_kv = nullptr;
+            TG_TRY(bridge->own.alloc(&d_kv, t.capacity * (int64_t)sizeof(SlotKV)));
+            hipLaunchKernelGGL(k_build_slotkv, dim3(tg_grid_for(t.capacity)),
+                               dim3(TG_BLOCK), 0, s->stream, t, d_kv);
+            TG_HIP_CHECK(hipGetLastError());
+            t.kv = d_kv;
+        }
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        return TG_OK;
+    }
+
+    /* legacy open-addressing table (TG_JOIN_CSR=0, and every empty build) */
+    tg_status build_open_addressing()
+    {
+        JoinTable& t = bridge->t;
+        hipLaunchKernelGGL(k_join_init, dim3(tg_grid_for(t.capacity)), dim3(TG_BLOCK),
+                           0, s->stream, t.slots, t.capacity, t.links, total_rows);
+        TG_HIP_CHECK(hipGetLastError());
+        if (total_rows > 0) {
+            hipLaunchKernelGGL(k_join_build, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
+                               0, s->stream, t);
+            TG_HIP_CHECK(hipGetLastError());
+        }
         return TG_OK;
     }
 
     tg_status add_input(const tg_page* page) override
     {
         DevPage in;
-        tg_status st = tg_upload_page(s, page, &in);
-        if (st != TG_OK) return st;
+        PageGuard gin(s, in);
+        TG_TRY(tg_upload_page(s, page, &in));
         total_rows += in.n;
-        pages.emplace_back(std::move(in));
+        pages.emplace_back(gin.take());
         return TG_OK;
     }
 
@@ -999,7 +1213,6 @@ struct HashBuilderOp : tg_operator {
     {
         if (input_finished) return TG_OK;
         input_finished = true;
-        /* concatenate channels (contiguous by global build row) + key copy */
         JoinTable& t = bridge->t;
         t.n = total_rows;
         t.capacity = join_hash_size(total_rows);
@@ -1013,222 +1226,30 @@ struct HashBuilderOp : tg_operator {
                        (long long)total_rows, (long long)t.capacity);
             return TG_ERR_OOM;
         }
-        static int pre_csr = [] { const char* e = getenv("TG_JOIN_CSR"); return e ? atoi(e) : 1; }();
-        if (!(pre_csr && total_rows > 0)) {
-            TG_POOL_ALLOC(s, &t.slots, t.capacity * 4);
-            TG_POOL_ALLOC(s, &t.links, (total_rows ? total_rows : 1) * 4);
-        }
-        TG_POOL_ALLOC(s, &t.keys, (total_rows ? total_rows : 1) * 8);
-        bool any_key_null = false;
-        for (auto& p : pages)
-            if (!p.blocks.empty() && p.blocks[key_channels[0]].valid) any_key_null = true;
-        if (any_key_null) {
-            int64_t words = (total_rows + 63) / 64;
-            TG_POOL_ALLOC(s, &t.key_valid, words * 8);
-            TG_HIP_CHECK(hipMemsetAsync(t.key_valid, 0xFF, words * 8, s->stream));
-        }
-        /* concat all channels */
+        TG_TRY(alloc_table());
         bridge->build_channels.resize(types.size());
-        for (size_t c = 0; c < types.size(); c++) {
-            DevBlock& b = bridge->build_channels[c];
-            b.type = types[c];
-            b.n = total_rows;
-            if (types[c] == TG_VARCHAR) {
-                tg_status vst = concat_varchar(c, &b);
-                if (vst != TG_OK) return vst;
-                continue;
-            }
-            TG_POOL_ALLOC(s, &b.data, (total_rows ? total_rows : 1) * b.elem_size());
-            int64_t at = 0;
-            bool anynull = false;
-            for (auto& p : pages) anynull |= p.blocks[c].valid != nullptr;
-            if (anynull) {
-                int64_t words = (total_rows + 63) / 64;
-                TG_POOL_ALLOC(s, &b.valid, words * 8);
-                TG_HIP_CHECK(hipMemsetAsync(b.valid, 0xFF, words * 8, s->stream));
-            }
-            for (auto& p : pages) {
-                TG_HIP_CHECK(hipMemcpyAsync((char*)b.data + at * b.elem_size(),
-                                            p.blocks[c].data, p.n * b.elem_size(),
-                                            hipMemcpyDeviceToDevice, s->stream));
-                /* null bitmaps land at arbitrary bit offsets: k_bitmap_concat
-                 * clears bit (at + i) per null row, whatever the page sizes */
-                if (p.blocks[c].valid) {
-                    hipLaunchKernelGGL(k_bitmap_concat, dim3(tg_grid_for(p.n)),
-                                       dim3(TG_BLOCK), 0, s->stream, p.blocks[c].valid,
-                                       p.n, at, b.valid);
-                    TG_HIP_CHECK(hipGetLastError());
-                }
-                at += p.n;
-            }
-        }
-        /* single BIGINT key -> BigintPagesHash-style flat key copy;
-         * otherwise the DefaultPagesHash-style generic channel compare
-         * (requires the CSR table; the legacy open-addressing path stays
-         * single-key). */
-        t.generic = !(key_channels.size() == 1 &&
-                      bridge->build_channels[key_channels[0]].type == TG_BIGINT);
-        t.n_key_ch = (int32_t)key_channels.size();
-        if (t.generic) {
-            DevPage view;   /* non-owning view over the concatenated channels */
-            view.n = total_rows;
-            view.blocks = bridge->build_channels;
-            for (auto& b : view.blocks) b.owned = false;
-            tg_status kst = make_kcols(s, view, key_channels.data(),
-                                       (int)key_channels.size(), &bridge->d_bkeys);
-            view.blocks.clear();
-            if (kst != TG_OK) return kst;
-            t.bkeys = bridge->d_bkeys;
-        }
-        else {
-            const DevBlock& kb = bridge->build_channels[key_channels[0]];
-            TG_HIP_CHECK(hipMemcpyAsync(t.keys, kb.data, total_rows * 8,
-                                        hipMemcpyDeviceToDevice, s->stream));
-            if (t.key_valid && kb.valid) {
-                TG_HIP_CHECK(hipMemcpyAsync(t.key_valid, kb.valid,
-                                            (total_rows + 63) / 64 * 8,
-                                            hipMemcpyDeviceToDevice, s->stream));
-            }
-        }
-        /* A/B on MI355X (Q3 SF100): CSR 98.0 ms/step vs open addressing
-         * 110.1 — CSR default; TG_JOIN_CSR=0 selects the legacy path */
-        static int use_csr = [] { const char* e = getenv("TG_JOIN_CSR"); return e ? atoi(e) : 1; }();
-        if (t.generic && !use_csr) { TG_SET_ERR("generic join keys require the CSR table"); return TG_ERR_UNSUPPORTED; }
-        /* SetBuilderOperator path: dense-range membership bitmap replaces
-         * the positional index entirely (the 380M-row Q4 build spent ~63 ms
-         * in CSR construction a semi join never needs) */
+        for (size_t c = 0; c < types.size(); c++)
+            TG_TRY(concat_channel(c, &bridge->build_channels[c]));
+        TG_TRY(copy_keys());
+        /* SetBuilderOperator path: the bitmap replaces the positional index
+         * entirely (the 380M-row Q4 build spent ~63 ms in CSR construction a
+         * semi join never needs). Beside a real index the bitmap is the
+         * dynamic filter requested via tg_join_bridge_request_bitmap. */
         bool bitmap_built = false;
-        if (set_only && !t.generic && total_rows > 0) {
-            tg_status mst = compute_key_range();
-            if (mst != TG_OK) return mst;
-            int64_t range = bridge->key_rows > 0
-                          ? bridge->key_max - bridge->key_min + 1 : 0;
-            if (range > 0 && range <= (1ll << 33)) {   /* <= 1 GiB bitmap */
-                int64_t words = (range + 63) / 64;
-                uint64_t* bm = nullptr;
-                TG_POOL_ALLOC(s, &bm, words * 8);
-                TG_HIP_CHECK(hipMemsetAsync(bm, 0, words * 8, s->stream));
-                hipLaunchKernelGGL(k_set_bits, dim3(tg_grid_for(total_rows)),
-                                   dim3(TG_BLOCK), 0, s->stream, t.keys,
-                                   t.key_valid, total_rows, bridge->key_min, bm);
-                TG_HIP_CHECK(hipGetLastError());
-                TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-                t.set_bitmap = bm;
-                t.set_min = bridge->key_min;
-                t.set_max = bridge->key_max;
+        if (!t.generic && total_rows > 0 && (set_only || bridge->want_bitmap)) {
+            TG_TRY(build_key_bitmap());
+            if (set_only && t.set_bitmap) {
                 t.has_null_key = bridge->key_rows < total_rows ? 1 : 0;
                 bitmap_built = true;
             }
         }
-        /* dynamic-filter bitmap alongside the real index (requested via
-         * tg_join_bridge_request_bitmap; single int64 key, dense range) */
-        if (!set_only && bridge->want_bitmap && !t.generic && total_rows > 0) {
-            tg_status mst = compute_key_range();
-            if (mst != TG_OK) return mst;
-            int64_t range = bridge->key_rows > 0
-                          ? bridge->key_max - bridge->key_min + 1 : 0;
-            if (range > 0 && range <= (1ll << 33)) {
-                int64_t words = (range + 63) / 64;
-                uint64_t* bm = nullptr;
-                TG_POOL_ALLOC(s, &bm, words * 8);
-                TG_HIP_CHECK(hipMemsetAsync(bm, 0, words * 8, s->stream));
-                hipLaunchKernelGGL(k_set_bits, dim3(tg_grid_for(total_rows)),
-                                   dim3(TG_BLOCK), 0, s->stream, t.keys,
-                                   t.key_valid, total_rows, bridge->key_min, bm);
-                TG_HIP_CHECK(hipGetLastError());
-                TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-                t.set_bitmap = bm;
-                t.set_min = bridge->key_min;
-                t.set_max = bridge->key_max;
-            }
-        }
-        if (!bitmap_built && use_csr && total_rows > 0) {
-            t.csr = 1;
-            int64_t region_slots = t.capacity < JREG_SLOTS ? t.capacity : JREG_SLOTS;
-            int64_t nreg = t.capacity / region_slots;
-            TG_POOL_ALLOC(s, &t.bucket_off, (t.capacity + 1) * 4);
-            TG_POOL_ALLOC(s, &t.csr_rows, total_rows * 4);
-            uint32_t* d_slot_of = nullptr;
-            int32_t* d_cnt = nullptr;       /* per-slot counts, then cursors */
-            int32_t* d_rtotal = nullptr;
-            int32_t* d_rbase = nullptr;
-            TG_POOL_ALLOC(s, &d_slot_of, total_rows * 4);
-            TG_POOL_ALLOC(s, &d_cnt, t.capacity * 4);
-            TG_POOL_ALLOC(s, &d_rtotal, nreg * 4);
-            TG_POOL_ALLOC(s, &d_rbase, nreg * 4);
-            TG_HIP_CHECK(hipMemsetAsync(d_cnt, 0, t.capacity * 4, s->stream));
-            hipLaunchKernelGGL(k_jc_count, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
-                               0, s->stream, t, d_slot_of, d_cnt);
-            TG_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_jc_local_off, dim3((uint32_t)nreg), dim3(TG_BLOCK),
-                               0, s->stream, d_cnt, t.bucket_off, d_rtotal,
-                               nreg, region_slots);
-            TG_HIP_CHECK(hipGetLastError());
-            std::vector<int32_t> rt(nreg), rb(nreg);
-            TG_HIP_CHECK(hipMemcpyAsync(rt.data(), d_rtotal, nreg * 4,
-                                        hipMemcpyDeviceToHost, s->stream));
-            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-            int32_t run = 0;
-            for (int64_t r = 0; r < nreg; r++) { rb[r] = run; run += rt[r]; }
-            int32_t total_indexed = run;    /* == total_rows minus null keys */
-            t.has_null_key = (int64_t)total_indexed < total_rows ? 1 : 0;
-            TG_HIP_CHECK(hipMemcpyAsync(d_rbase, rb.data(), nreg * 4,
-                                        hipMemcpyHostToDevice, s->stream));
-            hipLaunchKernelGGL(k_jc_addbase, dim3(tg_grid_for(t.capacity)), dim3(TG_BLOCK),
-                               0, s->stream, t.bucket_off, t.capacity, d_rbase,
-                               region_slots);
-            TG_HIP_CHECK(hipGetLastError());
-            TG_HIP_CHECK(hipMemcpyAsync(t.bucket_off + t.capacity, &total_indexed, 4,
-                                        hipMemcpyHostToDevice, s->stream));
-            TG_HIP_CHECK(hipMemcpyAsync(d_cnt, t.bucket_off, t.capacity * 4,
-                                        hipMemcpyDeviceToDevice, s->stream));
-            hipLaunchKernelGGL(k_jc_scatter, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
-                               0, s->stream, t, d_slot_of, d_cnt);
-            TG_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_jc_sort, dim3(tg_grid_for(t.capacity)), dim3(TG_BLOCK),
-                               0, s->stream, t);
-            TG_HIP_CHECK(hipGetLastError());
-            if (!t.generic && total_rows > 0) {
-                TG_POOL_ALLOC(s, &t.csr_keys, total_rows * 8);
-                hipLaunchKernelGGL(k_csr_keys, dim3(tg_grid_for(total_rows)),
-                                   dim3(TG_BLOCK), 0, s->stream, t, t.csr_keys);
-                TG_HIP_CHECK(hipGetLastError());
-            }
-            /* A/B on MI355X (Q3 SF100): the 512 MB kv array RAISED probe
-             * time (43.1 vs 39.7 ms per 10 launches) — the CSR arrays it
-             * replaces are smaller and L2-cache better. Kept behind
-             * TG_JOIN_KV=1 for small-table workloads. */
-            static int use_kv = [] { const char* e = getenv("TG_JOIN_KV"); return e ? atoi(e) : 0; }();
-            if (!t.generic && use_kv) {
-                SlotKV* d_kv = nullptr;
-                TG_POOL_ALLOC(s, &d_kv, t.capacity * (int64_t)sizeof(SlotKV));
-                hipLaunchKernelGGL(k_build_slotkv, dim3(tg_grid_for(t.capacity)),
-                                   dim3(TG_BLOCK), 0, s->stream, t, d_kv);
-                TG_HIP_CHECK(hipGetLastError());
-                t.kv = d_kv;
-            }
-            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-            tg_pool_free(s, d_slot_of);
-            tg_pool_free(s, d_cnt);
-            tg_pool_free(s, d_rtotal);
-            tg_pool_free(s, d_rbase);
-        }
-        else if (!bitmap_built) {
-            hipLaunchKernelGGL(k_join_init, dim3(tg_grid_for(t.capacity)), dim3(TG_BLOCK),
-                               0, s->stream, t.slots, t.capacity, t.links, total_rows);
-            TG_HIP_CHECK(hipGetLastError());
-            if (total_rows > 0) {
-                hipLaunchKernelGGL(k_join_build, dim3(tg_grid_for(total_rows)), dim3(TG_BLOCK),
-                                   0, s->stream, t);
-                TG_HIP_CHECK(hipGetLastError());
-            }
+        if (!bitmap_built) {
+            if (join_use_csr() && total_rows > 0) TG_TRY(build_csr());
+            else TG_TRY(build_open_addressing());
         }
         /* dynamic filter source: min/max over non-null build keys
          * (single-BIGINT-key builds; generic keys report no range) */
-        if (!t.generic && !range_done_) {
-            tg_status mst = compute_key_range();
-            if (mst != TG_OK) return mst;
-        }
+        if (!t.generic && !range_done_) TG_TRY(compute_key_range());
         /* the legacy open-addressing build counts no indexed rows: take the
          * semi join's "build has a NULL key" from the non-null key count */
         if (!t.generic && !t.csr && !bitmap_built)
@@ -1277,158 +1298,164 @@ struct LookupJoinOp : tg_operator {
         return TG_OK;
     }
 
-    tg_status add_input(const tg_page* page) override
+    /* Each probe path fills *d_op / *d_ob (probe row, build row per match,
+     * owned by `out`) and *total; its own temporaries end with it, so they
+     * are out of the pool's live set during the gathers. */
+
+    /* partitioned single-pass probe + stable match sort */
+    tg_status probe_partitioned(int64_t m, const ProbeKeys& pkc, int64_t tbl_bytes,
+                                PoolScratch& out, int32_t** d_op, int32_t** d_ob,
+                                int64_t* total)
     {
-        if (!bridge->built) { TG_SET_ERR("lookup source not built (finish the builder first)"); return TG_ERR_STATE; }
-        if (bridge_is_set_only(bridge)) { TG_SET_ERR("set-builder bridge supports semi join only"); return TG_ERR_UNSUPPORTED; }
-        tg_status st = check_probe_keys(bridge, page, key_channels.data(),
-                                        key_channels.size());
-        if (st != TG_OK) return st;
-        if (!record) bridge->plain_probed = true;
-        DevPage in;
-        st = tg_upload_page(s, page, &in);
-        if (st != TG_OK) return st;
-        JoinTable& t = bridge->t;
-        ProbeKeys pkc{};
-        KColH* d_pkg = nullptr;
-        if (t.generic) {
-            st = make_kcols(s, in, key_channels.data(), (int)key_channels.size(), &d_pkg);
-            if (st != TG_OK) { tg_free_page(s, &in); return st; }
-            pkc.pkg = d_pkg;
+        const JoinTable& t = bridge->t;
+        PoolScratch scratch(s);
+        int64_t nparts = 1;
+        while (tbl_bytes / nparts > (16ll << 20)) nparts <<= 1;
+        if (nparts > t.capacity) nparts = t.capacity;
+        int shift = 0;
+        while (((int64_t)1 << shift) < t.capacity / nparts) shift++;
+        uint32_t* d_slot_of = nullptr;
+        int32_t* d_pc = nullptr;
+        uint32_t* d_pi = nullptr;
+        uint32_t* d_ps = nullptr;
+        int64_t* d_pk = nullptr;
+        unsigned long long* d_cnt = nullptr;
+        TG_TRY(scratch.alloc(&d_slot_of, m * 4));
+        TG_TRY(scratch.alloc(&d_pc, (nparts + 1) * 4));
+        TG_TRY(scratch.alloc(&d_pi, m * 4));
+        TG_TRY(scratch.alloc(&d_ps, m * 4));
+        TG_TRY(scratch.alloc(&d_pk, m * 8));
+        TG_TRY(scratch.alloc(&d_cnt, 8));
+        TG_HIP_CHECK(hipMemsetAsync(d_pc, 0, (nparts + 1) * 4, s->stream));
+        TG_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, s->stream));
+        hipLaunchKernelGGL(k_pb_slots, dim3(tg_grid_for(m)), dim3(TG_BLOCK),
+                           (size_t)nparts * 4, s->stream, t, pkc, m, nparts,
+                           shift, d_slot_of, d_pc);
+        TG_HIP_CHECK(hipGetLastError());
+        std::vector<int32_t> pc(nparts), pb(nparts);
+        TG_HIP_CHECK(hipMemcpyAsync(pc.data(), d_pc, nparts * 4,
+                                    hipMemcpyDeviceToHost, s->stream));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        int32_t run = 0;
+        for (int64_t q = 0; q < nparts; q++) { pb[q] = run; run += pc[q]; }
+        int64_t midx = run;               /* non-null probe rows */
+        TG_HIP_CHECK(hipMemcpyAsync(d_pc, pb.data(), nparts * 4,
+                                    hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(k_pb_scatter, dim3(2048), dim3(TG_BLOCK),
+                           (size_t)nparts * 4, s->stream, t, pkc, m, shift,
+                           d_slot_of, d_pc, nparts, d_pi, d_ps, d_pk);
+        TG_HIP_CHECK(hipGetLastError());
+        /* one k_pb_probe launch per non-empty partition, into lists of `cap` */
+        auto probe_all = [&](int64_t cap) -> tg_status {
+            for (int64_t q = 0; q < nparts; q++) {
+                if (!pc[q]) continue;
+                hipLaunchKernelGGL(k_pb_probe, dim3(1024), dim3(TG_BLOCK), 0, s->stream,
+                                   t, (int64_t)pb[q], (int64_t)pb[q] + pc[q],
+                                   d_pi, d_ps, d_pk, d_cnt, cap,
+                                   (uint32_t*)*d_op, *d_ob);
+                TG_HIP_CHECK(hipGetLastError());
+            }
+            return TG_OK;
+        };
+        /* first-try match cap (exact when build keys are unique, the
+           usual case); k_pb_probe counts past it without writing, so an
+           overflow is detected and retried with the exact size */
+        int64_t cap = midx + t.n + 64;
+        TG_TRY(out.alloc(d_op, cap * 4));
+        TG_TRY(out.alloc(d_ob, cap * 4));
+        TG_TRY(probe_all(cap));
+        unsigned long long cnt = 0;
+        TG_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, s->stream));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        *total = (int64_t)cnt;
+        if (*total > cap) {      /* many-to-many overflow: exact retry */
+            out.release(*d_op);  /* back to the pool before the exact size is taken */
+            out.release(*d_ob);
+            cap = *total;
+            TG_TRY(out.alloc(d_op, cap * 4));
+            TG_TRY(out.alloc(d_ob, cap * 4));
+            TG_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, s->stream));
+            TG_TRY(probe_all(cap));
+            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
         }
-        else {
-            const DevBlock& kb = in.blocks[key_channels[0]];
-            if (kb.type != TG_BIGINT) { tg_free_page(s, &in); TG_SET_ERR("single join key must be BIGINT (use multi-channel keys otherwise)"); return TG_ERR_UNSUPPORTED; }
-            pkc.pk = (const int64_t*)kb.data;
-            pkc.pvalid = kb.valid;
-        }
+        return run_sort_pairs_u32(s, (uint32_t*)*d_op, *d_ob, *total);
+    }
+
+    /* two-pass probe: count matches per probe row, scan, fill */
+    tg_status probe_classic(int64_t m, const ProbeKeys& pkc, PoolScratch& out,
+                            int32_t** d_op, int32_t** d_ob, int64_t* total)
+    {
+        const JoinTable& t = bridge->t;
+        PoolScratch scratch(s);
         int32_t* d_counts = nullptr;
         int32_t* d_heads = nullptr;
         int64_t* d_offsets = nullptr;
         int64_t* d_total = nullptr;
-        int32_t* d_op = nullptr;
-        int32_t* d_ob = nullptr;
-        int64_t total = 0;
-        int64_t tbl_bytes = t.capacity * 4 + t.n * 12;
-        /* A/B on MI355X (Q3 SF100): partitioned probe 41 ms/step vs classic
-         * 28.6 — the ~300 MB table already rides the 256 MB LLC, so the
-         * extra partition passes (5.6 GB) and match sort never pay back.
-         * Kept behind TG_JOIN_PART=1 for tables that outgrow the LLC. */
+        TG_TRY(scratch.alloc(&d_counts, m * 4));
+        TG_TRY(scratch.alloc(&d_heads, m * 4));
+        TG_TRY(scratch.alloc(&d_offsets, m * 8));
+        TG_TRY(scratch.alloc(&d_total, 8));
+        hipLaunchKernelGGL(k_probe_count, dim3(tg_grid_for(m)), dim3(TG_BLOCK),
+                           0, s->stream, t, pkc, m, outer ? 1 : 0,
+                           d_counts, d_heads);
+        TG_HIP_CHECK(hipGetLastError());
+        TG_TRY(run_scan_counts(s, d_counts, m, d_offsets, d_total));
+        TG_HIP_CHECK(hipMemcpyAsync(total, d_total, 8, hipMemcpyDeviceToHost, s->stream));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        TG_TRY(out.alloc(d_op, *total * 4));
+        TG_TRY(out.alloc(d_ob, *total * 4));
+        hipLaunchKernelGGL(k_probe_fill, dim3(tg_grid_for(m)), dim3(TG_BLOCK),
+                           0, s->stream, t, pkc, m, d_heads, d_offsets, *d_op, *d_ob);
+        TG_HIP_CHECK(hipGetLastError());
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        return TG_OK;
+    }
+
+    /* A/B on MI355X (Q3 SF100): partitioned probe 41 ms/step vs classic
+     * 28.6 — the ~300 MB table already rides the 256 MB LLC, so the
+     * extra partition passes (5.6 GB) and match sort never pay back.
+     * Kept behind TG_JOIN_PART=1 for tables that outgrow the LLC. The
+     * switches are read per call. */
+    bool wants_partitioned(int64_t m, int64_t tbl_bytes) const
+    {
+        const JoinTable& t = bridge->t;
         const char* ep = getenv("TG_JOIN_PART");
         int use_part = ep ? atoi(ep) : 0;
         const char* emr = getenv("TG_JOIN_PART_MIN_ROWS");
         int64_t min_rows = emr ? atoll(emr) : (1 << 22);
         const char* emb = getenv("TG_JOIN_PART_MIN_BYTES");
         int64_t min_bytes = emb ? atoll(emb) : (64ll << 20);
-        if (use_part && !outer && t.csr && !t.generic && t.csr_keys &&
-            in.n >= min_rows && tbl_bytes > min_bytes) {
-            /* partitioned single-pass probe + stable match sort */
-            int64_t nparts = 1;
-            while (tbl_bytes / nparts > (16ll << 20)) nparts <<= 1;
-            if (nparts > t.capacity) nparts = t.capacity;
-            int shift = 0;
-            while (((int64_t)1 << shift) < t.capacity / nparts) shift++;
-            uint32_t* d_slot_of = nullptr;
-            int32_t* d_pc = nullptr;
-            uint32_t* d_pi = nullptr;
-            uint32_t* d_ps = nullptr;
-            int64_t* d_pk = nullptr;
-            unsigned long long* d_cnt = nullptr;
-            TG_POOL_ALLOC(s, &d_slot_of, in.n * 4);
-            TG_POOL_ALLOC(s, &d_pc, (nparts + 1) * 4);
-            TG_POOL_ALLOC(s, &d_pi, in.n * 4);
-            TG_POOL_ALLOC(s, &d_ps, in.n * 4);
-            TG_POOL_ALLOC(s, &d_pk, in.n * 8);
-            TG_POOL_ALLOC(s, &d_cnt, 8);
-            TG_HIP_CHECK(hipMemsetAsync(d_pc, 0, (nparts + 1) * 4, s->stream));
-            TG_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, s->stream));
-            hipLaunchKernelGGL(k_pb_slots, dim3(tg_grid_for(in.n)), dim3(TG_BLOCK),
-                               (size_t)nparts * 4, s->stream, t, pkc, in.n, nparts,
-                               shift, d_slot_of, d_pc);
-            TG_HIP_CHECK(hipGetLastError());
-            std::vector<int32_t> pc(nparts), pb(nparts);
-            TG_HIP_CHECK(hipMemcpyAsync(pc.data(), d_pc, nparts * 4,
-                                        hipMemcpyDeviceToHost, s->stream));
-            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-            int32_t run = 0;
-            for (int64_t q = 0; q < nparts; q++) { pb[q] = run; run += pc[q]; }
-            int64_t midx = run;               /* non-null probe rows */
-            TG_HIP_CHECK(hipMemcpyAsync(d_pc, pb.data(), nparts * 4,
-                                        hipMemcpyHostToDevice, s->stream));
-            hipLaunchKernelGGL(k_pb_scatter, dim3(2048), dim3(TG_BLOCK),
-                               (size_t)nparts * 4, s->stream, t, pkc, in.n, shift,
-                               d_slot_of, d_pc, nparts, d_pi, d_ps, d_pk);
-            TG_HIP_CHECK(hipGetLastError());
-            /* first-try match cap (exact when build keys are unique, the
-               usual case); k_pb_probe counts past it without writing, so an
-               overflow is detected and retried with the exact size */
-            int64_t cap = midx + t.n + 64;
-            TG_POOL_ALLOC(s, &d_op, cap * 4);
-            TG_POOL_ALLOC(s, &d_ob, cap * 4);
-            for (int64_t q = 0; q < nparts; q++) {
-                if (!pc[q]) continue;
-                hipLaunchKernelGGL(k_pb_probe, dim3(1024), dim3(TG_BLOCK), 0, s->stream,
-                                   t, (int64_t)pb[q], (int64_t)pb[q] + pc[q],
-                                   d_pi, d_ps, d_pk, d_cnt, cap,
-                                   (uint32_t*)d_op, d_ob);
-                TG_HIP_CHECK(hipGetLastError());
-            }
-            unsigned long long cnt = 0;
-            TG_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, s->stream));
-            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-            total = (int64_t)cnt;
-            if (total > cap) {       /* many-to-many overflow: exact retry */
-                tg_pool_free(s, d_op);
-                tg_pool_free(s, d_ob);
-                cap = total;
-                TG_POOL_ALLOC(s, &d_op, cap * 4);
-                TG_POOL_ALLOC(s, &d_ob, cap * 4);
-                TG_HIP_CHECK(hipMemsetAsync(d_cnt, 0, 8, s->stream));
-                for (int64_t q = 0; q < nparts; q++) {
-                    if (!pc[q]) continue;
-                    hipLaunchKernelGGL(k_pb_probe, dim3(1024), dim3(TG_BLOCK), 0, s->stream,
-                                       t, (int64_t)pb[q], (int64_t)pb[q] + pc[q],
-                                       d_pi, d_ps, d_pk, d_cnt, cap,
-                                       (uint32_t*)d_op, d_ob);
-                    TG_HIP_CHECK(hipGetLastError());
-                }
-                TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-            }
-            tg_status pst = run_sort_pairs_u32(s, (uint32_t*)d_op, d_ob, total);
-            if (pst != TG_OK) return pst;
-            tg_pool_free(s, d_slot_of);
-            tg_pool_free(s, d_pc);
-            tg_pool_free(s, d_pi);
-            tg_pool_free(s, d_ps);
-            tg_pool_free(s, d_pk);
-            tg_pool_free(s, d_cnt);
-        }
-        else {
-            TG_POOL_ALLOC(s, &d_counts, (in.n ? in.n : 1) * 4);
-            TG_POOL_ALLOC(s, &d_heads, (in.n ? in.n : 1) * 4);
-            TG_POOL_ALLOC(s, &d_offsets, (in.n ? in.n : 1) * 8);
-            TG_POOL_ALLOC(s, &d_total, 8);
-            hipLaunchKernelGGL(k_probe_count, dim3(tg_grid_for(in.n)), dim3(TG_BLOCK),
-                               0, s->stream, t, pkc, in.n, outer ? 1 : 0,
-                               d_counts, d_heads);
-            TG_HIP_CHECK(hipGetLastError());
-            tg_status sst = run_scan_counts(s, d_counts, in.n, d_offsets, d_total);
-            if (sst != TG_OK) return sst;
-            TG_HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s->stream));
-            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-            TG_POOL_ALLOC(s, &d_op, (total ? total : 1) * 4);
-            TG_POOL_ALLOC(s, &d_ob, (total ? total : 1) * 4);
-            hipLaunchKernelGGL(k_probe_fill, dim3(tg_grid_for(in.n)), dim3(TG_BLOCK),
-                               0, s->stream, t, pkc, in.n, d_heads, d_offsets, d_op, d_ob);
-            TG_HIP_CHECK(hipGetLastError());
-            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-        }
+        return use_part && !outer && t.csr && !t.generic && t.csr_keys &&
+               m >= min_rows && tbl_bytes > min_bytes;
+    }
+
+    tg_status add_input(const tg_page* page) override
+    {
+        if (!bridge->built) { TG_SET_ERR("lookup source not built (finish the builder first)"); return TG_ERR_STATE; }
+        if (bridge_is_set_only(bridge)) { TG_SET_ERR("set-builder bridge supports semi join only"); return TG_ERR_UNSUPPORTED; }
+        TG_TRY(check_probe_keys(bridge, page, key_channels.data(), key_channels.size()));
+        if (!record) bridge->plain_probed = true;
+        DevPage in, outp;
+        PageGuard gin(s, in), gout(s, outp);
+        PoolScratch scratch(s);          /* after the pages: destroyed, and drained, first */
+        TG_TRY(tg_upload_page(s, page, &in));
+        const JoinTable& t = bridge->t;
+        ProbeKeys pkc{};
+        TG_TRY(probe_keys_of(s, t, in, key_channels.data(), (int)key_channels.size(),
+                             scratch, &pkc));
+        int32_t* d_op = nullptr;
+        int32_t* d_ob = nullptr;
+        int64_t total = 0;
+        int64_t tbl_bytes = t.capacity * 4 + t.n * 12;
+        if (wants_partitioned(in.n, tbl_bytes))
+            TG_TRY(probe_partitioned(in.n, pkc, tbl_bytes, scratch, &d_op, &d_ob, &total));
+        else
+            TG_TRY(probe_classic(in.n, pkc, scratch, &d_op, &d_ob, &total));
 
         /* build-outer: whichever path ran, d_ob[0..total) is the matched
          * build row list — record it (stream-ordered before the gathers) */
         if (record) {
-            st = bridge_ensure_visited(bridge);
-            if (st != TG_OK) return st;
+            TG_TRY(bridge_ensure_visited(bridge));
             if (total > 0) {
                 hipLaunchKernelGGL(k_mark_visited, dim3(tg_grid_for(total)), dim3(TG_BLOCK),
                                    0, s->stream, d_ob, total, bridge->visited);
@@ -1438,30 +1465,17 @@ struct LookupJoinOp : tg_operator {
 
         /* output: probe output channels gathered by probe row, then build
          * output channels gathered by build row (LookupJoinPageBuilder) */
-        DevPage outp;
         outp.n = total;
         for (int32_t ch : probe_output) {
-            DevBlock ob;
-            st = run_gather(s, in.blocks[ch], d_op, (int32_t)total, &ob);
-            if (st != TG_OK) return st;
-            outp.blocks.push_back(ob);
+            outp.blocks.emplace_back();
+            TG_TRY(run_gather(s, in.blocks[ch], d_op, (int32_t)total, &outp.blocks.back()));
         }
         for (int32_t ch : bridge->build_output_channels) {
-            DevBlock ob;
-            st = run_gather(s, bridge->build_channels[ch], d_ob, (int32_t)total, &ob,
-                            outer /* -1 positions become NULL */);
-            if (st != TG_OK) return st;
-            outp.blocks.push_back(ob);
+            outp.blocks.emplace_back();
+            TG_TRY(run_gather(s, bridge->build_channels[ch], d_ob, (int32_t)total,
+                              &outp.blocks.back(), outer /* -1 positions become NULL */));
         }
-        if (d_counts) tg_pool_free(s, d_counts);
-        if (d_heads) tg_pool_free(s, d_heads);
-        if (d_offsets) tg_pool_free(s, d_offsets);
-        if (d_total) tg_pool_free(s, d_total);
-        if (d_pkg) tg_pool_free(s, d_pkg);
-        tg_pool_free(s, d_op);
-        tg_pool_free(s, d_ob);
-        tg_free_page(s, &in);
-        stage_output(std::move(outp));
+        stage_output(gout.take());
         return TG_OK;
     }
 
@@ -1521,50 +1535,42 @@ struct LookupOuterOp : tg_operator {
         const int64_t n = bridge->t.n;
         if (n == 0) return TG_OK;
         /* no recording operator ever added a page: every row is unvisited */
-        tg_status st = bridge_ensure_visited(bridge);
-        if (st != TG_OK) return st;
+        TG_TRY(bridge_ensure_visited(bridge));
+        DevPage outp;
+        PageGuard gout(s, outp);
+        PoolScratch scratch(s);
         int64_t words = (n + 63) / 64;
         int32_t* d_counts = nullptr;
         int64_t* d_offsets = nullptr;
         int64_t* d_total = nullptr;
-        TG_POOL_ALLOC(s, &d_counts, words * 4);
-        TG_POOL_ALLOC(s, &d_offsets, words * 8);
-        TG_POOL_ALLOC(s, &d_total, 8);
+        TG_TRY(scratch.alloc(&d_counts, words * 4));
+        TG_TRY(scratch.alloc(&d_offsets, words * 8));
+        TG_TRY(scratch.alloc(&d_total, 8));
         hipLaunchKernelGGL(k_unvisited_count, dim3(tg_grid_for(words)), dim3(TG_BLOCK),
                            0, s->stream, bridge->visited, n, d_counts);
         TG_HIP_CHECK(hipGetLastError());
-        st = run_scan_counts(s, d_counts, words, d_offsets, d_total);
-        if (st != TG_OK) return st;
+        TG_TRY(run_scan_counts(s, d_counts, words, d_offsets, d_total));
         int64_t total = 0;
         TG_HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s->stream));
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-        if (total > 0) {
-            int32_t* d_rows = nullptr;
-            TG_POOL_ALLOC(s, &d_rows, total * 4);
-            hipLaunchKernelGGL(k_unvisited_rows, dim3(tg_grid_for(words)), dim3(TG_BLOCK),
-                               0, s->stream, bridge->visited, n, d_offsets, d_rows);
-            TG_HIP_CHECK(hipGetLastError());
-            DevPage outp;
-            outp.n = total;
-            for (tg_type ty : probe_out_types) {
-                DevBlock ob;
-                st = null_column(ty, total, &ob);
-                if (st != TG_OK) return st;
-                outp.blocks.push_back(ob);
-            }
-            for (int32_t ch : bridge->build_output_channels) {
-                DevBlock ob;
-                st = run_gather(s, bridge->build_channels[ch], d_rows, (int32_t)total, &ob);
-                if (st != TG_OK) return st;
-                outp.blocks.push_back(ob);
-            }
-            TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-            tg_pool_free(s, d_rows);
-            stage_output(std::move(outp));
+        if (total == 0) return TG_OK;
+        int32_t* d_rows = nullptr;
+        TG_TRY(scratch.alloc(&d_rows, total * 4));
+        hipLaunchKernelGGL(k_unvisited_rows, dim3(tg_grid_for(words)), dim3(TG_BLOCK),
+                           0, s->stream, bridge->visited, n, d_offsets, d_rows);
+        TG_HIP_CHECK(hipGetLastError());
+        outp.n = total;
+        for (tg_type ty : probe_out_types) {
+            outp.blocks.emplace_back();
+            TG_TRY(null_column(ty, total, &outp.blocks.back()));
         }
-        tg_pool_free(s, d_counts);
-        tg_pool_free(s, d_offsets);
-        tg_pool_free(s, d_total);
+        for (int32_t ch : bridge->build_output_channels) {
+            outp.blocks.emplace_back();
+            TG_TRY(run_gather(s, bridge->build_channels[ch], d_rows, (int32_t)total,
+                              &outp.blocks.back()));
+        }
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        stage_output(gout.take());
         return TG_OK;
     }
 
@@ -1583,8 +1589,7 @@ struct LookupOuterOp : tg_operator {
                 TG_SET_ERR("a join_type 0 or 1 lookup join probed this bridge: its matches were not recorded");
                 return TG_ERR_STATE;
             }
-            tg_status st = emit_unmatched();
-            if (st != TG_OK) return st;
+            TG_TRY(emit_unmatched());
             emitted = true;
             input_finished = true;
         }
@@ -1601,52 +1606,14 @@ struct LookupOuterOp : tg_operator {
 extern "C" tg_status tg_join_bridge_create(tg_session* s, tg_join_bridge** out)
 {
     if (!s || !out) { TG_SET_ERR("null arg"); return TG_ERR_INVALID_ARG; }
-    auto* b = new tg_join_bridge();
-    b->s = s;
-    *out = b;
+    *out = new tg_join_bridge(s);
     return TG_OK;
 }
 
+/* the bridge's owner drains the stream and frees every table buffer */
 extern "C" void tg_join_bridge_close(tg_join_bridge* b)
 {
-    if (!b) return;
-    if (b->t.slots) tg_pool_free(b->s, b->t.slots);
-    if (b->t.links) tg_pool_free(b->s, b->t.links);
-    if (b->t.keys) tg_pool_free(b->s, b->t.keys);
-    if (b->t.key_valid) tg_pool_free(b->s, b->t.key_valid);
-    if (b->t.bucket_off) tg_pool_free(b->s, b->t.bucket_off);
-    if (b->t.csr_rows) tg_pool_free(b->s, b->t.csr_rows);
-    if (b->t.csr_keys) tg_pool_free(b->s, b->t.csr_keys);
-    if (b->t.kv) tg_pool_free(b->s, (void*)b->t.kv);
-    if (b->t.set_bitmap) tg_pool_free(b->s, (void*)b->t.set_bitmap);
-    if (b->d_bkeys) tg_pool_free(b->s, b->d_bkeys);
-    if (b->visited) tg_pool_free(b->s, b->visited);
-    for (auto& c : b->build_channels) {
-        if (c.data) tg_pool_free(b->s, c.data);
-        if (c.valid) tg_pool_free(b->s, c.valid);
-        if (c.offsets) tg_pool_free(b->s, c.offsets);
-    }
     delete b;
-}
-
-extern "C" tg_status tg_hash_builder_create(tg_session* s, tg_join_bridge* bridge,
-    const int32_t* build_types, int32_t n_build_channels,
-    const int32_t* key_channels, int32_t n_key_channels,
-    const int32_t* output_channels, int32_t n_output_channels,
-    tg_operator** out);
-
-/* SetBuilderOperator analog (semi-join source: ChannelSet membership only;
- * dense key ranges use a bitmap, sparse ranges fall back to the CSR index) */
-extern "C" tg_status tg_set_builder_create(tg_session* s, tg_join_bridge* bridge,
-    const int32_t* build_types, int32_t n_build_channels,
-    int32_t key_channel, tg_operator** out)
-{
-    int32_t kc = key_channel;
-    tg_status st = tg_hash_builder_create(s, bridge, build_types, n_build_channels,
-                                          &kc, 1, nullptr, 0, out);
-    if (st != TG_OK) return st;
-    static_cast<HashBuilderOp*>(*out)->set_only = true;
-    return TG_OK;
 }
 
 extern "C" tg_status tg_hash_builder_create(tg_session* s, tg_join_bridge* bridge,
@@ -1670,6 +1637,19 @@ extern "C" tg_status tg_hash_builder_create(tg_session* s, tg_join_bridge* bridg
     bridge->key_channels = op->key_channels;
     bridge->build_output_channels.assign(output_channels, output_channels + n_output_channels);
     *out = op;
+    return TG_OK;
+}
+
+/* SetBuilderOperator analog (semi-join source: ChannelSet membership only;
+ * dense key ranges use a bitmap, sparse ranges fall back to the CSR index) */
+extern "C" tg_status tg_set_builder_create(tg_session* s, tg_join_bridge* bridge,
+    const int32_t* build_types, int32_t n_build_channels,
+    int32_t key_channel, tg_operator** out)
+{
+    int32_t kc = key_channel;
+    TG_TRY(tg_hash_builder_create(s, bridge, build_types, n_build_channels,
+                                  &kc, 1, nullptr, 0, out));
+    static_cast<HashBuilderOp*>(*out)->set_only = true;
     return TG_OK;
 }
 
@@ -1751,27 +1731,17 @@ struct SemiJoinOp : tg_operator {
                        bridge->key_channels.size());
             return TG_ERR_UNSUPPORTED;
         }
-        tg_status st = check_probe_keys(bridge, page, &key_channel, 1);
-        if (st != TG_OK) return st;
+        TG_TRY(check_probe_keys(bridge, page, &key_channel, 1));
         DevPage in;
-        st = tg_upload_page(s, page, &in);
-        if (st != TG_OK) return st;
-        JoinTable& jt = bridge->t;
+        PageGuard gin(s, in);
+        PoolScratch scratch(s);
+        TG_TRY(tg_upload_page(s, page, &in));
         ProbeKeys pkc{};
-        KColH* d_pkg = nullptr;
-        if (jt.generic) {
-            int32_t kcs[1] = {key_channel};
-            st = make_kcols(s, in, kcs, 1, &d_pkg);
-            if (st != TG_OK) { tg_free_page(s, &in); return st; }
-            pkc.pkg = d_pkg;
-        }
-        else {
-            const DevBlock& kb0 = in.blocks[key_channel];
-            if (kb0.type != TG_BIGINT) { tg_free_page(s, &in); TG_SET_ERR("semi join single key must be BIGINT"); return TG_ERR_UNSUPPORTED; }
-            pkc.pk = (const int64_t*)kb0.data;
-            pkc.pvalid = kb0.valid;
-        }
-        DevBlock mb;
+        TG_TRY(probe_keys_of(s, bridge->t, in, &key_channel, 1, scratch, &pkc));
+        /* the match channel is appended to the guarded probe page, which then
+         * moves into the output whole: its blocks and the match */
+        in.blocks.emplace_back();
+        DevBlock& mb = in.blocks.back();
         mb.type = TG_BOOLEAN;
         mb.n = in.n;
         TG_POOL_ALLOC(s, &mb.data, in.n ? in.n : 1);
@@ -1782,13 +1752,7 @@ struct SemiJoinOp : tg_operator {
                            0, s->stream, bridge->t, pkc, in.n, (int8_t*)mb.data, mb.valid);
         TG_HIP_CHECK(hipGetLastError());
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
-        if (d_pkg) tg_pool_free(s, d_pkg);
-        DevPage outp;
-        outp.n = in.n;
-        for (auto& b : in.blocks) { outp.blocks.push_back(b); }
-        in.blocks.clear();                /* ownership moved */
-        outp.blocks.push_back(mb);
-        stage_output(std::move(outp));
+        stage_output(gin.take());
         return TG_OK;
     }
 
@@ -1815,13 +1779,6 @@ extern "C" tg_status tg_semi_join_create(tg_session* s, tg_join_bridge* bridge,
     *out = op;
     return TG_OK;
 }
-
-extern "C" tg_status tg_lookup_join_create_ex(tg_session* s, tg_join_bridge* bridge,
-    const int32_t* probe_types, int32_t n_probe_channels,
-    const int32_t* key_channels, int32_t n_key_channels,
-    const int32_t* probe_output_channels, int32_t n_probe_output,
-    int32_t join_type /* 0 inner, 1 probe-outer, 2 build-outer, 3 full */,
-    tg_operator** out);
 
 extern "C" tg_status tg_lookup_join_create(tg_session* s, tg_join_bridge* bridge,
     const int32_t* probe_types, int32_t n_probe_channels,
@@ -1854,10 +1811,9 @@ extern "C" tg_status tg_lookup_join_create_ex(tg_session* s, tg_join_bridge* bri
         TG_SET_ERR("join_type %d: 0 inner, 1 probe-outer, 2 build-outer, 3 full", join_type);
         return TG_ERR_INVALID_ARG;
     }
-    tg_status st = tg_lookup_join_create(s, bridge, probe_types, n_probe_channels,
-                                         key_channels, n_key_channels,
-                                         probe_output_channels, n_probe_output, out);
-    if (st != TG_OK) return st;
+    TG_TRY(tg_lookup_join_create(s, bridge, probe_types, n_probe_channels,
+                                 key_channels, n_key_channels,
+                                 probe_output_channels, n_probe_output, out));
     auto* op = static_cast<LookupJoinOp*>(*out);
     op->outer = (join_type == 1 || join_type == 3);
     if (join_type >= 2) {    /* build-outer: counted until finished or closed */
