@@ -241,6 +241,45 @@ tg_status tg_lookup_join_create_ex(tg_session*, tg_join_bridge*,
     const int32_t* key_channels, int32_t n_key_channels,
     const int32_t* probe_output_channels, int32_t n_probe_output,
     int32_t join_type, tg_operator** out);
+/* tg_lookup_join_create_ex with a residual filter on the join condition
+ * (JoinFilterFunction: `ON a.k = b.k AND <filter>`; LookupJoinOperator tests
+ * it on every position of the link chain before a pair counts as a match).
+ * filter == NULL is exactly tg_lookup_join_create_ex.
+ * Column addressing: `filter` is a program of the expression IR above (same
+ * opcodes, 6 stack slots, Kleene logic). TG_EXPR_COL index c names probe page
+ * channel c when c < n_probe_channels, and build channel c - n_probe_channels
+ * otherwise. Build channels are the channels given to tg_hash_builder_create,
+ * all of them, not only the build output channels; probe channels need not be
+ * probe output channels either.
+ * Match rule: a candidate pair (probe row i, build row r) with equal keys is
+ * a match iff the filter, evaluated on the cells of i and r, is non-NULL and
+ * non-zero (the filter operator's keep rule). The output is the unfiltered
+ * inner output with the failing pairs removed and nothing else moved: probe
+ * rows ascending, the build rows of one probe row in the unfiltered order.
+ * join_type 1 / 3: a probe row with no surviving pair emits one NULL-build
+ * row at its place in probe order, whether its key is NULL, has no equal
+ * build key, or had candidates that all failed the filter.
+ * join_type 2 / 3: only surviving pairs are recorded on the bridge, so a
+ * build row whose candidates all failed is emitted by tg_lookup_outer_create,
+ * which is unchanged. Operators with different filters may share a bridge:
+ * the visited set is the union of their surviving pairs.
+ * Validation, before anything is launched. At create: the program checks of
+ * tg_filter_project_create, where a program that does not reduce to one value
+ * or needs more than 6 stack slots is TG_ERR_INVALID_ARG and an opcode
+ * outside 0..16 is TG_ERR_UNSUPPORTED; join_type as tg_lookup_join_create_ex.
+ * At add_input (page types and the built bridge are known then): a column
+ * index outside n_probe_channels + build channels, or a probe index outside
+ * the page, is TG_ERR_INVALID_ARG; a VARCHAR channel named by the filter is
+ * TG_ERR_UNSUPPORTED. More than INT32_MAX candidate pairs (equal-key pairs
+ * before the filter) or output rows for one page is TG_ERR_UNSUPPORTED on
+ * this path, never a silent cast. */
+tg_status tg_lookup_join_create_filtered(tg_session*, tg_join_bridge*,
+    const int32_t* probe_types, int32_t n_probe_channels,
+    const int32_t* key_channels, int32_t n_key_channels,
+    const int32_t* probe_output_channels, int32_t n_probe_output,
+    int32_t join_type,            /* 0..3 as tg_lookup_join_create_ex */
+    const tg_expr* filter,        /* NULL: exactly tg_lookup_join_create_ex */
+    tg_operator** out);
 /* Lookup-outer operator (operator/join/LookupOuterOperator.java): the source
  * operator that completes a RIGHT or FULL join. It emits one row for every
  * build row that no probe row matched, build rows whose key has a NULL or a

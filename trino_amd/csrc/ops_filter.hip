@@ -13,10 +13,8 @@
  *    interpreter over the tg_expr IR (stack depth <= MAX_STACK, opcodes and
  *    column indices checked on the host before any launch).
  */
-#include "operators.h"
+#include "expr_eval.h"   /* KCol, TVal, load_tcol, eval_expr: shared with the join filter */
 #include <cstdlib>
-
-struct KCol { const void* data; const uint64_t* valid; int32_t type; int32_t _pad; };
 
 /* fused dynamic filter (sql/gen/columnar/DynamicPageFilter.java analog):
  * membership bitmap over a dense build-key range, tested INSIDE the scan
@@ -41,129 +39,7 @@ __device__ static inline bool df_test(const DF& df, const KCol* cols, int64_t i)
 }
 
 #define MAX_STACK 6
-
-/* Typed stack value: BIGINT/INTEGER/DATE/… stay in an exact int64 lane
- * (mirrors sql/gen/columnar/CallColumnarFilterGenerator.java:160-198 which
- * compiles the comparison at the column's Java type — long compares are
- * exact there, so they must be exact here; keys above 2^53 would silently
- * lose precision in a double lane). `f` mirrors the value for mixed-type
- * ops (Trino coerces BIGINT to DOUBLE in mixed expressions). */
-struct TVal { double f; int64_t i; bool isint; bool null; };
-
-__device__ static inline TVal load_tcol(const KCol& c, int64_t i)
-{
-    TVal v;
-    v.null = c.valid && !((c.valid[i >> 6] >> (i & 63)) & 1);
-    if (v.null) { v.f = 0.0; v.i = 0; v.isint = true; return v; }
-    switch (c.type) {
-        case TG_BIGINT: v.i = ((const int64_t*)c.data)[i]; v.isint = true; v.f = (double)v.i; break;
-        case TG_INTEGER: case TG_DATE: v.i = ((const int32_t*)c.data)[i]; v.isint = true; v.f = (double)v.i; break;
-        case TG_SMALLINT: v.i = ((const int16_t*)c.data)[i]; v.isint = true; v.f = (double)v.i; break;
-        case TG_TINYINT: case TG_BOOLEAN: v.i = ((const int8_t*)c.data)[i]; v.isint = true; v.f = (double)v.i; break;
-        default: v.f = ((const double*)c.data)[i]; v.i = 0; v.isint = false; break;
-    }
-    return v;
-}
-
-__device__ static inline bool tval_truthy(const TVal& v) { return v.isint ? v.i != 0 : v.f != 0.0; }
-
-/* postfix interpreter; returns a typed value. Integer ops are exact int64
- * (incl. BIGINT/BIGINT truncated division); mixed int/double coerces to
- * double. Comparisons compare in int64 iff both sides are int. AND/OR/NOT
- * follow SQL Kleene three-valued logic (io.trino.sql.ir.Logical semantics:
- * AND — false dominates null; OR — true dominates null; NOT null = null),
- * so compositions under NOT are correct; a null FILTER result rejects the
- * row at the call site (CallColumnarFilterGenerator's nullable loop). */
-__device__ static TVal eval_expr(const tg_expr_inst* prog, int count,
-                                 const KCol* cols, int64_t row)
-{
-    TVal s0{}, s1{}, s2{}, s3{}, s4{}, s5{};
-    int sp = 0;
-#define PUSH(v) do { switch (sp) { \
-        case 0: s0 = (v); break; case 1: s1 = (v); break; \
-        case 2: s2 = (v); break; case 3: s3 = (v); break; \
-        case 4: s4 = (v); break; default: s5 = (v); break; } \
-        sp++; } while (0)
-#define TOP (sp == 1 ? s0 : sp == 2 ? s1 : sp == 3 ? s2 : sp == 4 ? s3 \
-             : sp == 5 ? s4 : s5)
-#define POP(v) do { v = TOP; sp--; } while (0)
-#define ARITH(expr_i, expr_f) do { TVal r; r.null = a.null | b.null; \
-        r.isint = a.isint & b.isint; \
-        if (r.isint) { r.i = (expr_i); r.f = (double)r.i; } \
-        else { r.f = (expr_f); r.i = 0; } PUSH(r); } while (0)
-#define CMP(op_) do { TVal r; r.null = a.null | b.null; r.isint = true; \
-        r.i = (a.isint & b.isint) ? (a.i op_ b.i ? 1 : 0) \
-                                  : (a.f op_ b.f ? 1 : 0); \
-        r.f = (double)r.i; PUSH(r); } while (0)
-
-    for (int k = 0; k < count; k++) {
-        tg_expr_inst in = prog[k];
-        TVal a, b, c;
-        switch (in.op) {
-            case TG_EXPR_COL: PUSH(load_tcol(cols[in.arg0], row)); break;
-            case TG_EXPR_CONST_F64: { TVal v; v.f = in.imm.f64; v.i = 0; v.isint = false; v.null = false; PUSH(v); break; }
-            case TG_EXPR_CONST_I64: { TVal v; v.i = in.imm.i64; v.f = (double)v.i; v.isint = true; v.null = false; PUSH(v); break; }
-            case TG_EXPR_ADD: POP(b); POP(a); ARITH(a.i + b.i, a.f + b.f); break;
-            case TG_EXPR_SUB: POP(b); POP(a); ARITH(a.i - b.i, a.f - b.f); break;
-            case TG_EXPR_MUL: POP(b); POP(a); ARITH(a.i * b.i, a.f * b.f); break;
-            case TG_EXPR_DIV: POP(b); POP(a); {
-                TVal r; r.isint = a.isint & b.isint;
-                if (r.isint) {   /* BIGINT/BIGINT truncates; /0 poisons to null
-                                    (the C-ABI has no per-row error channel;
-                                    Trino raises DIVISION_BY_ZERO) */
-                    r.null = a.null | b.null | (b.i == 0);
-                    r.i = (b.i == 0) ? 0 : a.i / b.i;
-                    r.f = (double)r.i;
-                }
-                else { r.null = a.null | b.null; r.f = a.f / b.f; r.i = 0; }
-                PUSH(r); break;
-            }
-            case TG_EXPR_LE: POP(b); POP(a); CMP(<=); break;
-            case TG_EXPR_LT: POP(b); POP(a); CMP(<); break;
-            case TG_EXPR_GE: POP(b); POP(a); CMP(>=); break;
-            case TG_EXPR_GT: POP(b); POP(a); CMP(>); break;
-            case TG_EXPR_EQ: POP(b); POP(a); CMP(==); break;
-            case TG_EXPR_NE: POP(b); POP(a); CMP(!=); break;
-            case TG_EXPR_AND: { POP(b); POP(a);
-                bool af = !a.null && !tval_truthy(a), bf = !b.null && !tval_truthy(b);
-                TVal r; r.isint = true;
-                r.null = !(af | bf) && (a.null | b.null);
-                r.i = (!r.null && !af && !bf) ? 1 : 0;
-                r.f = (double)r.i; PUSH(r); break;
-            }
-            case TG_EXPR_OR: { POP(b); POP(a);
-                bool at = !a.null && tval_truthy(a), bt = !b.null && tval_truthy(b);
-                TVal r; r.isint = true;
-                r.null = !(at | bt) && (a.null | b.null);
-                r.i = (at | bt) ? 1 : 0;
-                r.f = (double)r.i; PUSH(r); break;
-            }
-            case TG_EXPR_NOT: { POP(a);
-                TVal r; r.isint = true; r.null = a.null;
-                r.i = (!a.null && !tval_truthy(a)) ? 1 : 0;
-                r.f = (double)r.i; PUSH(r); break;
-            }
-            case TG_EXPR_BETWEEN: { POP(c); POP(b); POP(a);
-                /* a >= b AND a <= c under Kleene AND, typed compares */
-                bool ge, le, ge_n = a.null | b.null, le_n = a.null | c.null;
-                ge = (a.isint & b.isint) ? a.i >= b.i : a.f >= b.f;
-                le = (a.isint & c.isint) ? a.i <= c.i : a.f <= c.f;
-                bool af = !ge_n && !ge, bf = !le_n && !le;
-                TVal r; r.isint = true;
-                r.null = !(af | bf) && (ge_n | le_n);
-                r.i = (!r.null && !af && !bf) ? 1 : 0;
-                r.f = (double)r.i; PUSH(r); break;
-            }
-            default: break;
-        }
-    }
-    return TOP;
-#undef PUSH
-#undef POP
-#undef TOP
-#undef ARITH
-#undef CMP
-}
+static_assert(MAX_STACK == EXPR_STACK_SLOTS, "check_expr_depth admits what the interpreter holds");
 
 /* row index for the k-th selected input position */
 __device__ static inline int64_t sel_row(int has_list, const int32_t* list,
@@ -1215,7 +1091,7 @@ struct FilterProjectOp : tg_operator {
     }
 };
 
-static tg_status check_expr_depth(const tg_expr* e)
+tg_status check_expr_depth(const tg_expr* e, tg_status too_deep)
 {
     int sp = 0, maxsp = 0;
     if (!e->insts || e->count < 1) { TG_SET_ERR("empty expr"); return TG_ERR_INVALID_ARG; }
@@ -1239,7 +1115,7 @@ static tg_status check_expr_depth(const tg_expr* e)
         if (sp > maxsp) maxsp = sp;
         if (sp < 1) { TG_SET_ERR("expr stack underflow at inst %d", i); return TG_ERR_INVALID_ARG; }
     }
-    if (maxsp > MAX_STACK) { TG_SET_ERR("expr stack depth %d > %d", maxsp, MAX_STACK); return TG_ERR_UNSUPPORTED; }
+    if (maxsp > MAX_STACK) { TG_SET_ERR("expr stack depth %d > %d", maxsp, MAX_STACK); return too_deep; }
     if (sp != 1) { TG_SET_ERR("expr does not reduce to one value"); return TG_ERR_INVALID_ARG; }
     return TG_OK;
 }

@@ -20,8 +20,13 @@
  *    match; per probe row the head match is emitted then the chain is walked.
  *    Output assembly mirrors LookupJoinPageBuilder.java:89-119: probe columns
  *    gathered by probe position, build columns gathered by synthetic address.
+ *  - join filter: JoinFilterFunction.filter(left, right, page), which the
+ *    reference tests on every position of the link chain; here one step
+ *    (LookupJoinOp::filter_matches) on the candidate list every probe path
+ *    ends in, before the visited marks and the gathers.
  */
 #include "dev_hash.h"
+#include "expr_eval.h"
 
 /* inline single-entry bucket (the common case: unique build keys): one
  * aligned 16-byte random read resolves most probes instead of three
@@ -889,6 +894,106 @@ __global__ void k_unvisited_rows(const uint64_t* __restrict__ visited, int64_t n
     }
 }
 
+/* ---- residual join filter (JoinFilterFunction: LookupJoinOperator tests it
+ * on every position of the link chain before a pair counts as a match).
+ * Every probe path ends in one probe-ordered candidate list (op, ob, n); the
+ * kernels below turn it into the surviving list, so the step is as
+ * path-independent as k_mark_visited, which then runs on the survivors.
+ * All of them are elementwise over pairs or probe rows and separated by
+ * launches; the scans between them are run_scan_counts. ---- */
+
+/* one lane per candidate pair: keep[j] = the filter on (probe row op[j],
+ * build row ob[j]) is non-NULL and non-zero (the filter operator's keep
+ * rule). op is ascending, so probe cells load near-sequentially; build cells
+ * are gathers. */
+__global__ void k_pair_filter(const tg_expr_inst* __restrict__ prog, int count,
+                              const KCol* __restrict__ pcols,
+                              const KCol* __restrict__ bcols, int32_t n_probe,
+                              const int32_t* __restrict__ op,
+                              const int32_t* __restrict__ ob, int64_t n,
+                              int32_t* __restrict__ keep)
+{
+    int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; j < n; j += stride) {
+        TVal v = eval_expr_cols(prog, count, PairCols{pcols, bcols, n_probe, op[j], ob[j]});
+        keep[j] = (!v.null && tval_truthy(v)) ? 1 : 0;
+    }
+}
+
+/* stable compaction by flag: kept pair j lands at at[j] + shift[op[j]]
+ * (shift null: inner / right, where at = the exclusive scan of keep is the
+ * whole position) */
+__global__ void k_pair_place(const int32_t* __restrict__ keep,
+                             const int64_t* __restrict__ at,
+                             const int64_t* __restrict__ shift,
+                             const int32_t* __restrict__ op,
+                             const int32_t* __restrict__ ob, int64_t n,
+                             int32_t* __restrict__ out_probe,
+                             int32_t* __restrict__ out_build)
+{
+    int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; j < n; j += stride) {
+        if (!keep[j]) continue;
+        int32_t i = op[j];
+        int64_t pos = at[j] + (shift ? shift[i] : 0);
+        out_probe[pos] = i;
+        out_build[pos] = ob[j];
+    }
+}
+
+/* survivors per probe row without an atomic: the candidates of probe row i
+ * are one run of equal op, so with F = the exclusive scan of keep the row's
+ * survivors are F[end] + keep[end] - F[start]. The run's first lane stores
+ * the one, its last lane the other; rows without a candidate keep the zeros
+ * both arrays were cleared to. (n <= INT32_MAX on this path, so F fits.) */
+__global__ void k_pair_seg_bounds(const int32_t* __restrict__ op,
+                                  const int32_t* __restrict__ keep,
+                                  const int64_t* __restrict__ F, int64_t n,
+                                  int32_t* __restrict__ seg_lo,
+                                  int32_t* __restrict__ seg_hi)
+{
+    int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; j < n; j += stride) {
+        int32_t i = op[j];
+        if (j == 0 || op[j - 1] != i) seg_lo[i] = (int32_t)F[j];
+        if (j == n - 1 || op[j + 1] != i) seg_hi[i] = (int32_t)F[j] + keep[j];
+    }
+}
+
+/* in place: seg_lo[i] -> surv[i], seg_hi[i] -> (surv[i] == 0) */
+__global__ void k_pair_survivors(int32_t* __restrict__ seg_lo,
+                                 int32_t* __restrict__ seg_hi, int64_t m)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < m; i += stride) {
+        int32_t surv = seg_hi[i] - seg_lo[i];
+        seg_lo[i] = surv;
+        seg_hi[i] = surv == 0;
+    }
+}
+
+/* probe-outer: the NULL-build row of survivor-less probe row i goes to
+ * S[i] + Z[i] (kept pairs of earlier probe rows + NULL rows of earlier ones) */
+__global__ void k_pair_null_rows(const int32_t* __restrict__ zero,
+                                 const int64_t* __restrict__ S,
+                                 const int64_t* __restrict__ Z, int64_t m,
+                                 int32_t* __restrict__ out_probe,
+                                 int32_t* __restrict__ out_build)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < m; i += stride) {
+        if (!zero[i]) continue;
+        int64_t pos = S[i] + Z[i];
+        out_probe[pos] = (int32_t)i;
+        out_build[pos] = -1;
+    }
+}
+
 /* allocate and zero the bridge's visited bitmap on first need */
 static tg_status bridge_ensure_visited(tg_join_bridge* b)
 {
@@ -1285,6 +1390,14 @@ struct LookupJoinOp : tg_operator {
     bool outer = false;             /* probe-outer (LEFT, FULL) */
     bool record = false;            /* build-outer (RIGHT, FULL): mark visited */
     bool counted = false;           /* still in bridge->recording */
+    /* residual filter (tg_lookup_join_create_filtered): the compiled program
+     * and the device array over ALL build channels live as long as the
+     * operator; the array is made at the first add_input, when the bridge is
+     * built */
+    bool has_filter = false;
+    ExprProgram filter{};
+    int32_t n_probe_channels = 0;   /* TG_EXPR_COL indices below it name the probe page */
+    KCol* d_bcols = nullptr;
 
     void release_recording()
     {
@@ -1368,6 +1481,7 @@ struct LookupJoinOp : tg_operator {
         TG_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, s->stream));
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
         *total = (int64_t)cnt;
+        TG_TRY(check_candidates(*total));
         if (*total > cap) {      /* many-to-many overflow: exact retry */
             out.release(*d_op);  /* back to the pool before the exact size is taken */
             out.release(*d_ob);
@@ -1382,8 +1496,9 @@ struct LookupJoinOp : tg_operator {
     }
 
     /* two-pass probe: count matches per probe row, scan, fill */
-    tg_status probe_classic(int64_t m, const ProbeKeys& pkc, PoolScratch& out,
-                            int32_t** d_op, int32_t** d_ob, int64_t* total)
+    tg_status probe_classic(int64_t m, const ProbeKeys& pkc, bool probe_outer,
+                            PoolScratch& out, int32_t** d_op, int32_t** d_ob,
+                            int64_t* total)
     {
         const JoinTable& t = bridge->t;
         PoolScratch scratch(s);
@@ -1396,18 +1511,158 @@ struct LookupJoinOp : tg_operator {
         TG_TRY(scratch.alloc(&d_offsets, m * 8));
         TG_TRY(scratch.alloc(&d_total, 8));
         hipLaunchKernelGGL(k_probe_count, dim3(tg_grid_for(m)), dim3(TG_BLOCK),
-                           0, s->stream, t, pkc, m, outer ? 1 : 0,
+                           0, s->stream, t, pkc, m, probe_outer ? 1 : 0,
                            d_counts, d_heads);
         TG_HIP_CHECK(hipGetLastError());
         TG_TRY(run_scan_counts(s, d_counts, m, d_offsets, d_total));
         TG_HIP_CHECK(hipMemcpyAsync(total, d_total, 8, hipMemcpyDeviceToHost, s->stream));
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        TG_TRY(check_candidates(*total));
         TG_TRY(out.alloc(d_op, *total * 4));
         TG_TRY(out.alloc(d_ob, *total * 4));
         hipLaunchKernelGGL(k_probe_fill, dim3(tg_grid_for(m)), dim3(TG_BLOCK),
                            0, s->stream, t, pkc, m, d_heads, d_offsets, *d_op, *d_ob);
         TG_HIP_CHECK(hipGetLastError());
         TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        return TG_OK;
+    }
+
+    /* the filtered path indexes its lists with int32 positions and hands the
+     * total to the int32 gathers: say so instead of casting */
+    tg_status check_candidates(int64_t total) const
+    {
+        if (has_filter && total > (int64_t)INT32_MAX) {
+            TG_SET_ERR("filtered lookup join: %lld candidate pairs for one page exceed "
+                       "INT32_MAX; probe with smaller pages", (long long)total);
+            return TG_ERR_UNSUPPORTED;
+        }
+        return TG_OK;
+    }
+
+    /* host-side checks of the filter against this page and the built bridge,
+     * before anything is uploaded or launched */
+    tg_status check_filter_page(const tg_page* page) const
+    {
+        const int32_t n_build = (int32_t)bridge->build_types.size();
+        for (int k = 0; k < filter.count; k++) {
+            if (filter.insts[k].op != TG_EXPR_COL) continue;
+            int32_t c = filter.insts[k].arg0;
+            int32_t type;
+            if (c >= 0 && c < n_probe_channels && c < page->channel_count)
+                type = (int32_t)page->blocks[c].type;
+            else if (c >= n_probe_channels && c - n_probe_channels < n_build)
+                type = (int32_t)bridge->build_types[c - n_probe_channels];
+            else {
+                TG_SET_ERR("join filter column index %d outside the %d probe + %d build "
+                           "channels (the page has %d)", c, n_probe_channels, n_build,
+                           page->channel_count);
+                return TG_ERR_INVALID_ARG;
+            }
+            if (type == TG_VARCHAR) {
+                TG_SET_ERR("VARCHAR channel %d in a join filter", c);
+                return TG_ERR_UNSUPPORTED;
+            }
+        }
+        return TG_OK;
+    }
+
+    /* device KCol array over every channel of `blocks`; the caller owns it */
+    tg_status upload_kcols(const std::vector<DevBlock>& blocks, KCol** d_out)
+    {
+        std::vector<KCol> cols(blocks.size());
+        for (size_t c = 0; c < blocks.size(); c++)
+            cols[c] = {blocks[c].data, blocks[c].valid, (int32_t)blocks[c].type, 0};
+        size_t bytes = (cols.size() ? cols.size() : 1) * sizeof(KCol);
+        TG_TRY(tg_pool_alloc(s, (void**)d_out, bytes));
+        if (!cols.empty()) {
+            TG_HIP_CHECK(hipMemcpyAsync(*d_out, cols.data(), cols.size() * sizeof(KCol),
+                                        hipMemcpyHostToDevice, s->stream));
+            TG_HIP_CHECK(hipStreamSynchronize(s->stream));   /* cols is a local */
+        }
+        return TG_OK;
+    }
+
+    /* The filter step: (d_op, d_ob, total) comes in as the inner candidate
+     * list of the page, probe rows ascending, and leaves as the match list
+     * the unfiltered operator would have produced had only the pairs that
+     * pass the filter been equal: failing pairs removed, nothing else moved,
+     * and under probe-outer one (i, -1) row for every probe row left without
+     * a pair, at its place. With F, S, Z the exclusive scans of keep over
+     * pairs, of survivors over probe rows and of (survivors == 0) over probe
+     * rows: kept pair j -> F[j] + Z[op[j]], NULL row of i -> S[i] + Z[i]. */
+    tg_status filter_matches(const DevPage& in, PoolScratch& out,
+                             int32_t** d_op, int32_t** d_ob, int64_t* total)
+    {
+        const int64_t n = *total, m = in.n;
+        if (n == 0 && !outer) return TG_OK;
+        PoolScratch scratch(s);
+        KCol* d_pcols = nullptr;
+        TG_TRY(upload_kcols(in.blocks, &d_pcols));
+        scratch.adopt(d_pcols);
+        int32_t* d_keep = nullptr;
+        int64_t* d_F = nullptr;
+        int64_t* d_tot = nullptr;       /* kept pairs, NULL rows */
+        TG_TRY(scratch.alloc(&d_keep, n * 4));
+        TG_TRY(scratch.alloc(&d_F, n * 8));
+        TG_TRY(scratch.alloc(&d_tot, 2 * 8));
+        if (n > 0) {
+            hipLaunchKernelGGL(k_pair_filter, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0,
+                               s->stream, filter.d_insts, filter.count, d_pcols, d_bcols,
+                               n_probe_channels, *d_op, *d_ob, n, d_keep);
+            TG_HIP_CHECK(hipGetLastError());
+        }
+        TG_TRY(run_scan_counts(s, d_keep, n, d_F, d_tot));
+        int32_t* d_surv = nullptr;      /* segment starts, then survivors per probe row */
+        int32_t* d_zero = nullptr;      /* segment ends, then survivors == 0 */
+        int64_t* d_S = nullptr;
+        int64_t* d_Z = nullptr;
+        if (outer) {
+            TG_TRY(scratch.alloc(&d_surv, m * 4));
+            TG_TRY(scratch.alloc(&d_zero, m * 4));
+            TG_TRY(scratch.alloc(&d_S, m * 8));
+            TG_TRY(scratch.alloc(&d_Z, m * 8));
+            TG_HIP_CHECK(hipMemsetAsync(d_surv, 0, m * 4, s->stream));
+            TG_HIP_CHECK(hipMemsetAsync(d_zero, 0, m * 4, s->stream));
+            if (n > 0) {
+                hipLaunchKernelGGL(k_pair_seg_bounds, dim3(tg_grid_for(n)), dim3(TG_BLOCK),
+                                   0, s->stream, *d_op, d_keep, d_F, n, d_surv, d_zero);
+                TG_HIP_CHECK(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_pair_survivors, dim3(tg_grid_for(m)), dim3(TG_BLOCK),
+                               0, s->stream, d_surv, d_zero, m);
+            TG_HIP_CHECK(hipGetLastError());
+            TG_TRY(run_scan_counts(s, d_surv, m, d_S, d_tot));   /* same total again */
+            TG_TRY(run_scan_counts(s, d_zero, m, d_Z, d_tot + 1));
+        }
+        int64_t tot[2] = {0, 0};
+        TG_HIP_CHECK(hipMemcpyAsync(tot, d_tot, outer ? 16 : 8, hipMemcpyDeviceToHost,
+                                    s->stream));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        const int64_t new_total = tot[0] + tot[1];
+        if (new_total > (int64_t)INT32_MAX) {
+            TG_SET_ERR("filtered lookup join: %lld output rows for one page exceed "
+                       "INT32_MAX; probe with smaller pages", (long long)new_total);
+            return TG_ERR_UNSUPPORTED;
+        }
+        int32_t* d_fp = nullptr;
+        int32_t* d_fb = nullptr;
+        TG_TRY(out.alloc(&d_fp, new_total * 4));
+        TG_TRY(out.alloc(&d_fb, new_total * 4));
+        if (n > 0 && tot[0] > 0) {
+            hipLaunchKernelGGL(k_pair_place, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0,
+                               s->stream, d_keep, d_F, d_Z, *d_op, *d_ob, n, d_fp, d_fb);
+            TG_HIP_CHECK(hipGetLastError());
+        }
+        if (outer && tot[1] > 0) {
+            hipLaunchKernelGGL(k_pair_null_rows, dim3(tg_grid_for(m)), dim3(TG_BLOCK), 0,
+                               s->stream, d_zero, d_S, d_Z, m, d_fp, d_fb);
+            TG_HIP_CHECK(hipGetLastError());
+        }
+        out.release(*d_op);     /* drains the stream: the candidates are done with */
+        out.release(*d_ob);
+        *d_op = d_fp;
+        *d_ob = d_fb;
+        *total = new_total;
         return TG_OK;
     }
 
@@ -1434,6 +1689,10 @@ struct LookupJoinOp : tg_operator {
         if (!bridge->built) { TG_SET_ERR("lookup source not built (finish the builder first)"); return TG_ERR_STATE; }
         if (bridge_is_set_only(bridge)) { TG_SET_ERR("set-builder bridge supports semi join only"); return TG_ERR_UNSUPPORTED; }
         TG_TRY(check_probe_keys(bridge, page, key_channels.data(), key_channels.size()));
+        if (has_filter) {
+            TG_TRY(check_filter_page(page));
+            if (!d_bcols) TG_TRY(upload_kcols(bridge->build_channels, &d_bcols));
+        }
         if (!record) bridge->plain_probed = true;
         DevPage in, outp;
         PageGuard gin(s, in), gout(s, outp);
@@ -1449,11 +1708,14 @@ struct LookupJoinOp : tg_operator {
         int64_t tbl_bytes = t.capacity * 4 + t.n * 12;
         if (wants_partitioned(in.n, tbl_bytes))
             TG_TRY(probe_partitioned(in.n, pkc, tbl_bytes, scratch, &d_op, &d_ob, &total));
-        else
-            TG_TRY(probe_classic(in.n, pkc, scratch, &d_op, &d_ob, &total));
+        else   /* with a filter the probe is inner: filter_matches adds the NULL rows */
+            TG_TRY(probe_classic(in.n, pkc, outer && !has_filter, scratch,
+                                 &d_op, &d_ob, &total));
+        if (has_filter)
+            TG_TRY(filter_matches(in, scratch, &d_op, &d_ob, &total));
 
         /* build-outer: whichever path ran, d_ob[0..total) is the matched
-         * build row list — record it (stream-ordered before the gathers) */
+         * build row list (after the filter: the surviving pairs only) — record it (stream-ordered before the gathers) */
         if (record) {
             TG_TRY(bridge_ensure_visited(bridge));
             if (total > 0) {
@@ -1488,6 +1750,8 @@ struct LookupJoinOp : tg_operator {
     ~LookupJoinOp() override
     {
         release_recording();     /* closed unfinished: the bridge outlives us */
+        if (has_filter) tg_free_expr(s, &filter);
+        if (d_bcols) tg_pool_free(s, d_bcols);
         for (auto& p : out_pages_) tg_free_page(s, &p);
     }
 };
@@ -1821,6 +2085,30 @@ extern "C" tg_status tg_lookup_join_create_ex(tg_session* s, tg_join_bridge* bri
         op->counted = true;
         bridge->recording++;
     }
+    return TG_OK;
+}
+
+/* tg_lookup_join_create_ex with a residual filter on the join condition */
+extern "C" tg_status tg_lookup_join_create_filtered(tg_session* s, tg_join_bridge* bridge,
+    const int32_t* probe_types, int32_t n_probe_channels,
+    const int32_t* key_channels, int32_t n_key_channels,
+    const int32_t* probe_output_channels, int32_t n_probe_output,
+    int32_t join_type, const tg_expr* filter, tg_operator** out)
+{
+    if (filter) {
+        if (n_probe_channels < 0) { TG_SET_ERR("n_probe_channels %d", n_probe_channels); return TG_ERR_INVALID_ARG; }
+        TG_TRY(check_expr_depth(filter, TG_ERR_INVALID_ARG));
+    }
+    TG_TRY(tg_lookup_join_create_ex(s, bridge, probe_types, n_probe_channels,
+                                    key_channels, n_key_channels,
+                                    probe_output_channels, n_probe_output,
+                                    join_type, out));
+    if (!filter) return TG_OK;
+    auto* op = static_cast<LookupJoinOp*>(*out);
+    tg_status st = tg_compile_expr(s, filter, &op->filter);
+    op->has_filter = true;       /* the destructor frees whatever was compiled */
+    op->n_probe_channels = n_probe_channels;
+    if (st != TG_OK) { delete op; *out = nullptr; return st; }
     return TG_OK;
 }
 

@@ -336,23 +336,44 @@ def hash_builder(session, bridge, build_types, key_channels, output_channels):
     return op
 
 
+_lib.tg_lookup_join_create_filtered.restype = ctypes.c_int
+_lib.tg_lookup_join_create_filtered.argtypes = (
+    [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_void_p, ctypes.c_int32] * 3
+    + [ctypes.c_int32, ctypes.POINTER(TgExpr), ctypes.c_void_p])
+
+
 def lookup_join(session, bridge, probe_types, key_channels, probe_output_channels,
-                join_type=0):
+                join_type=0, filter=None):
     """join_type: 0 inner, 1 probe-outer (LEFT), 2 build-outer (RIGHT),
     3 FULL. 2 and 3 emit what 0 and 1 emit and record the matched build rows
     on the bridge; once every such operator is finished (or closed),
     lookup_outer(session, bridge, ...) emits the build rows nobody matched.
     Close the operator before the bridge. Other values raise
-    (TG_ERR_INVALID_ARG)."""
+    (TG_ERR_INVALID_ARG).
+
+    filter: an expr(...) program, the residual term of the join condition
+    (`ON a.k = b.k AND <filter>`). ('col', c) names probe page channel c when
+    c < len(probe_types), else build channel c - len(probe_types), counted
+    over ALL channels given to hash_builder (not only its output channels).
+    A pair with equal keys is a match only if the filter is non-NULL and
+    non-zero on its two rows; under LEFT / FULL a probe row whose candidates
+    all fail comes out NULL-extended, under RIGHT / FULL a build row whose
+    candidates all fail is emitted by lookup_outer. VARCHAR channels cannot
+    be named. None is the unfiltered join."""
     h = ctypes.c_void_p()
     pt = _i32arr(probe_types)
     kc = _i32arr(key_channels)
     oc = _i32arr(probe_output_channels)
-    _check(_lib.tg_lookup_join_create_ex(session._h, bridge._h, pt.ctypes.data, len(pt),
-                                         kc.ctypes.data, len(kc), oc.ctypes.data,
-                                         len(oc), join_type, ctypes.byref(h)))
+    if filter is None:
+        _check(_lib.tg_lookup_join_create_ex(session._h, bridge._h, pt.ctypes.data, len(pt),
+                                             kc.ctypes.data, len(kc), oc.ctypes.data,
+                                             len(oc), join_type, ctypes.byref(h)))
+    else:
+        _check(_lib.tg_lookup_join_create_filtered(
+            session._h, bridge._h, pt.ctypes.data, len(pt), kc.ctypes.data, len(kc),
+            oc.ctypes.data, len(oc), join_type, ctypes.byref(filter), ctypes.byref(h)))
     op = Operator(session, h)
-    op._keep = (pt, kc, oc)
+    op._keep = (pt, kc, oc, filter)
     return op
 
 
