@@ -351,6 +351,16 @@ typedef struct tg_tpch_lineitem_cols {
     uint8_t* shipinstruct;  /* optional (flags bit 6): dictionary id 0..3 =
                                DELIVER IN PERSON,COLLECT COD,TAKE BACK
                                RETURN,NONE (pinned) */
+    /* Exact integer forms of the four numeric columns. All
+     * four are set or none is: tg_tpch_lineitem_alloc fills them when the
+     * memory is there, a struct built by hand leaves them NULL. Where they
+     * are set, the stated equality holds bit for bit for every row, and
+     * neither they nor their f64 columns are written after generation.
+     * tg_q1_run reads these 7 B/row instead of the 32 B/row of f64. */
+    uint8_t* quantity_u8;          /* (double)x         == quantity[i]      */
+    int32_t* extendedprice_cents;  /* (double)x / 100.0 == extendedprice[i] */
+    uint8_t* discount_pct;         /* (double)x / 100.0 == discount[i]      */
+    uint8_t* tax_pct;              /* (double)x / 100.0 == tax[i]           */
 } tg_tpch_lineitem_cols;
 
 /* Generate lineitem rows for orders [order_start, order_start+order_count)

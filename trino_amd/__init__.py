@@ -53,6 +53,12 @@ class LineitemCols(ctypes.Structure):
         ("tp_cents", ctypes.c_void_p),
         ("suppkey", ctypes.c_void_p),
         ("shipinstruct", ctypes.c_void_p),
+        # exact integer forms of quantity / extendedprice / discount / tax:
+        # all four set (by the generator) or all NULL (built by hand)
+        ("quantity_u8", ctypes.c_void_p),
+        ("extendedprice_cents", ctypes.c_void_p),
+        ("discount_pct", ctypes.c_void_p),
+        ("tax_pct", ctypes.c_void_p),
     ]
 
 

@@ -37,6 +37,12 @@
  * 4.19 -> 3.81 ms; scan 3.8 ms = 6.0 TB/s of the ~6.3 TB/s a streaming read
  * reaches; merge 4.6 us where the serial reduce + result copy took 0.14 ms.
  *
+ * k_q1_fused_int is the same step over the exact integer forms of the four
+ * numeric columns (13 B/row instead of 38): tg_q1_run launches it when the
+ * column set carries all four (the generator fills them), k_q1_fused
+ * otherwise; the 60 result words are identical. See "integer-column scan"
+ * below and profiles/q1_int_columns_vs_parent.txt.
+ *
  * Parity-mode kernel (k_q1_naive_seq): single thread, reference sequential
  * order — bit-equal to oracle o_q1_naive for page-sized operator tests.
  */
@@ -299,6 +305,277 @@ void k_q1_fused(int64_t n, const int32_t* __restrict__ shipdate,
     }
 }
 
+/* ---- integer-column scan ------------------------------------------------
+ * The same sums from the exact integer forms of the four numeric columns
+ * (tg_tpch_lineitem_cols: quantity_u8, extendedprice_cents, discount_pct,
+ * tax_pct): 13 B/row instead of 38. Every row's doubles are rebuilt bit for
+ * bit — e = cents/100.0, d = pct/100.0, t = pct/100.0 — and then go through
+ * exactly k_q1_fused's arithmetic, so the 60 result words are identical.
+ *
+ *   price       cents/100.0 without a divide: q0 = k*0.01, r = fma(-q0,100,k),
+ *               q = fma(r,0.01,q0) equals the IEEE quotient for every k in
+ *               [0, 2^31) (checked exhaustively on the host); plain k*0.01 is
+ *               wrong for 288,120,706 of them.
+ *   percentages a byte has 256 values: each block builds, with the f64 path's
+ *               own expressions, LDS tables of 1.0-d and trunc(d*2^59) by
+ *               discount byte and 1.0+t by tax byte; a row costs one
+ *               ds_read_b128 and one ds_read_b64 instead of two decodes, two
+ *               adds and one f64->u64 conversion.
+ *   quantity    the byte is the integer addend; no f64 at all.
+ *
+ * A lane takes Q1I_R rows per iteration (one or more dwordx4 of price and
+ * shipdate, Q1I_R/4 dwords of each byte column: every load is >= 4 B per lane
+ * and coalesced) and works through them four at a time with k_q1_fused's
+ * section scheme. Pipelining, nontemporal loads, compile-time combo indices,
+ * 96-bit sums and 32-bit counts are as in k_q1_fused.
+ *
+ * Measured at SF100 (profiles/q1_int_columns_vs_parent.txt):
+ * the scan is issue-bound, not HBM-bound. Q1I_R = 4 needs 166 VGPRs and runs
+ * 3 waves/SIMD, which beats 8 and 16 rows per lane at 2 waves/SIMD; the fma
+ * decode beats the divide; carry-free split sums (no s_nop hazard slots) and
+ * a bit-level trunc were built, verified and measured no gain at Q1I_R = 4. */
+#ifndef Q1I_R
+#define Q1I_R 4                    /* rows per lane per iteration: 4, 8 or 16 */
+#endif
+#define Q1I_GRID_CAP 1536          /* blocks; TG_Q1_BLOCKS overrides */
+#define Q1I_W (Q1I_R / 4)          /* dwords per byte column, dwordx4 per i32 column */
+static_assert(Q1I_R == 4 || Q1I_R == 8 || Q1I_R == 16, "Q1I_R: whole dwordx4 groups");
+
+struct q1i_rows {
+    q1_i32x4 pc[Q1I_W], sd[Q1I_W];
+    unsigned q[Q1I_W], d[Q1I_W], t[Q1I_W], rf[Q1I_W], ls[Q1I_W];   /* 4 packed bytes each */
+};
+
+/* Q1I_W consecutive dwords of a byte column as one load */
+__device__ static inline void q1i_load_bytes(unsigned (&w)[Q1I_W], const uint8_t* __restrict__ p)
+{
+#if Q1I_W == 1
+    w[0] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(p));
+#else
+    typedef unsigned wvec __attribute__((ext_vector_type(Q1I_W)));
+    const wvec v = __builtin_nontemporal_load(reinterpret_cast<const wvec*>(p));
+    #pragma unroll
+    for (int k = 0; k < Q1I_W; k++) w[k] = v[k];
+#endif
+}
+
+__device__ static inline void q1i_load(q1i_rows& g, int64_t r,
+                                       const int32_t* __restrict__ shipdate,
+                                       const int32_t* __restrict__ cents,
+                                       const uint8_t* __restrict__ qty,
+                                       const uint8_t* __restrict__ disc,
+                                       const uint8_t* __restrict__ tax,
+                                       const uint8_t* __restrict__ rflag,
+                                       const uint8_t* __restrict__ lstatus)
+{
+    const q1_i32x4* pp = reinterpret_cast<const q1_i32x4*>(cents + r);
+    const q1_i32x4* ps = reinterpret_cast<const q1_i32x4*>(shipdate + r);
+    #pragma unroll
+    for (int k = 0; k < Q1I_W; k++) {
+        g.pc[k] = __builtin_nontemporal_load(pp + k);
+        g.sd[k] = __builtin_nontemporal_load(ps + k);
+    }
+    q1i_load_bytes(g.q, qty + r);
+    q1i_load_bytes(g.d, disc + r);
+    q1i_load_bytes(g.t, tax + r);
+    q1i_load_bytes(g.rf, rflag + r);
+    q1i_load_bytes(g.ls, lstatus + r);
+}
+
+/* (double)k / 100.0 for 0 <= k < 2^31, bit for bit, without the divide */
+__device__ static inline double q1i_cents_to_double(int32_t k)
+{
+    const double kd = (double)k;
+    const double q0 = kd * 0.01;
+    const double r = __fma_rn(-q0, 100.0, kd);
+    return __fma_rn(r, 0.01, q0);
+}
+
+/* per-block decode tables, indexed by the column byte */
+struct q1i_tables {
+    ulonglong2 d[256];   /* .x = bits of 1.0 - d, .y = trunc(d * 2^59) */
+    double opt[256];     /* 1.0 + t */
+};
+
+__device__ static inline void q1i_build_tables(q1i_tables& tab)
+{
+    static_assert(TG_BLOCK == 256, "one table entry per thread");
+    const double v = (double)threadIdx.x / 100.0;   /* the generator's expression */
+    tab.d[threadIdx.x].x = (unsigned long long)__double_as_longlong(1.0 - v);
+    tab.d[threadIdx.x].y = fx_trunc(v, S59);
+    tab.opt[threadIdx.x] = 1.0 + v;
+    __syncthreads();
+}
+
+/* one row's five addends from its integers */
+__device__ static inline void q1i_row(const q1i_tables& tab, int32_t cents, unsigned dpct,
+                                      unsigned tpct, unsigned long long& yb,
+                                      unsigned long long& yp, unsigned long long& yc,
+                                      unsigned long long& yd)
+{
+    const double e = q1i_cents_to_double(cents);
+    const ulonglong2 dd = tab.d[dpct];
+    const double dp = e * __longlong_as_double((long long)dd.x);
+    const double ch = dp * tab.opt[tpct];
+    yb = fx_trunc(e, S43);
+    yp = fx_trunc(dp, S43);
+    yc = fx_trunc(ch, S43);
+    yd = dd.y;
+}
+
+/* four rows (one dword of each byte column) into the lane's accumulators */
+__device__ static inline void q1i_accumulate4(lane_acc (&acc)[NCOMBO], const q1i_tables& tab,
+                                              q1_i32x4 pc, q1_i32x4 sdv, unsigned qw,
+                                              unsigned dw, unsigned tw, unsigned rfw,
+                                              unsigned lsw, int32_t cutoff)
+{
+    const int32_t ce[4] = { pc.x, pc.y, pc.z, pc.w };
+    const int32_t sd[4] = { sdv.x, sdv.y, sdv.z, sdv.w };
+    unsigned sc[4];         /* combo of a selected row, 0xffff otherwise */
+    unsigned present = 0;   /* bit c: this lane has a selected row of combo c */
+    unsigned long long yb[4], yp[4], yc[4], yd[4];
+    unsigned yq[4];
+    #pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const unsigned cb = ((rfw >> (8 * j)) & 0xffu) * 2 + ((lsw >> (8 * j)) & 0xffu);
+        const bool sel = sd[j] <= cutoff;
+        sc[j] = sel ? cb : 0xffffu;
+        present |= sel ? (1u << (cb & 31u)) : 0u;
+        q1i_row(tab, ce[j], (dw >> (8 * j)) & 0xffu, (tw >> (8 * j)) & 0xffu,
+                yb[j], yp[j], yc[j], yd[j]);
+        yq[j] = (qw >> (8 * j)) & 0xffu;
+    }
+    #pragma unroll
+    for (int c = 0; c < NCOMBO; c++) {
+        if (__any((int)(present & (1u << c)))) {
+            #pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (sc[j] == (unsigned)c)
+                    Q1_ACC_ADD(c, yb[j], yp[j], yc[j], yd[j], yq[j], 1u);
+            }
+        }
+    }
+}
+
+/* wave -> block reduction of the lane accumulators and the block's word-major
+ * partials (integers: order-free, deterministic); k_q1_fused's epilogue */
+__device__ static inline void q1_block_reduce(const lane_acc (&acc)[NCOMBO],
+                                              unsigned long long (&lds)[TG_BLOCK / 64][PARTIAL_WORDS],
+                                              unsigned long long* __restrict__ partials)
+{
+    const int wave = threadIdx.x / 64;
+    const int lane = threadIdx.x % 64;
+    #pragma unroll
+    for (int c = 0; c < NCOMBO; c++) {
+        u128 b, p, h, d;
+        #define Q1_WIDEN(v, a) do { v.lo = ((unsigned long long)(a).w1 << 32) | (a).w0; v.hi = (a).w2; } while (0)
+        Q1_WIDEN(b, acc[c].base);
+        Q1_WIDEN(p, acc[c].dp);
+        Q1_WIDEN(h, acc[c].ch);
+        Q1_WIDEN(d, acc[c].disc);
+        #undef Q1_WIDEN
+        unsigned long long q = acc[c].qty, k = acc[c].cnt;
+        wave_reduce_u128(b);
+        wave_reduce_u128(p);
+        wave_reduce_u128(h);
+        wave_reduce_u128(d);
+        wave_reduce_u64(q);
+        wave_reduce_u64(k);
+        if (lane == 0) {
+            unsigned long long* w = lds[wave] + c * 10;
+            w[0] = b.lo; w[1] = b.hi;
+            w[2] = p.lo; w[3] = p.hi;
+            w[4] = h.lo; w[5] = h.hi;
+            w[6] = d.lo; w[7] = d.hi;
+            w[8] = q;    w[9] = k;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < PARTIAL_WORDS) {
+        const int f = threadIdx.x;          /* one word per thread */
+        unsigned long long* pw = partials + (int64_t)f * TG_MAX_BLOCKS + blockIdx.x;
+        if ((f % 10) < 8 && f % 2 == 0) {
+            /* lo word of a u128 field: sum los, carries go into the hi word,
+             * which this thread writes too */
+            unsigned long long lo = 0, hisum = 0;
+            #pragma unroll
+            for (int w = 0; w < TG_BLOCK / 64; w++) {
+                unsigned long long x = lds[w][f];
+                lo += x;
+                hisum += (lo < x);
+            }
+            #pragma unroll
+            for (int w = 0; w < TG_BLOCK / 64; w++) hisum += lds[w][f + 1];
+            pw[0] = lo;
+            pw[TG_MAX_BLOCKS] = hisum;
+        }
+        else if ((f % 10) >= 8) {
+            unsigned long long s = 0;
+            #pragma unroll
+            for (int w = 0; w < TG_BLOCK / 64; w++) s += lds[w][f];
+            pw[0] = s;
+        }
+    }
+}
+
+__global__ __launch_bounds__(TG_BLOCK, 2)   /* 2nd arg: waves/SIMD, at least */
+void k_q1_fused_int(int64_t n, const int32_t* __restrict__ shipdate,
+                    const uint8_t* __restrict__ qty, const int32_t* __restrict__ cents,
+                    const uint8_t* __restrict__ disc, const uint8_t* __restrict__ tax,
+                    const uint8_t* __restrict__ rflag, const uint8_t* __restrict__ lstatus,
+                    int32_t cutoff, unsigned long long* __restrict__ partials)
+{
+    __shared__ q1i_tables tab;
+    __shared__ unsigned long long lds[TG_BLOCK / 64][PARTIAL_WORDS];
+    q1i_build_tables(tab);
+
+    lane_acc acc[NCOMBO];
+    #pragma unroll
+    for (int c = 0; c < NCOMBO; c++) {
+        acc[c].base = acc[c].dp = acc[c].ch = acc[c].disc = acc96{0u, 0u, 0u};
+        acc[c].qty = 0;
+        acc[c].cnt = 0;
+    }
+
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;   /* lanes total */
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t ngrp = n / Q1I_R;
+
+    /* the pipeline of k_q1_fused: `nxt` receives group i + stride while `cur`
+     * is computed on; a lane's last iteration re-reads its own group (in
+     * bounds, discarded). No lane reads past row ngrp * Q1I_R <= n. */
+    if (gid < ngrp) {
+        int64_t i = gid;
+        q1i_rows cur, nxt;
+        q1i_load(cur, Q1I_R * i, shipdate, cents, qty, disc, tax, rflag, lstatus);
+        do {
+            const int64_t in = i + stride;
+            const int64_t ip = in < ngrp ? in : i;
+            q1i_load(nxt, Q1I_R * ip, shipdate, cents, qty, disc, tax, rflag, lstatus);
+            #pragma unroll
+            for (int k = 0; k < Q1I_W; k++)
+                q1i_accumulate4(acc, tab, cur.pc[k], cur.sd[k], cur.q[k], cur.d[k],
+                                cur.t[k], cur.rf[k], cur.ls[k], cutoff);
+            cur = nxt;
+            i = in;
+        } while (i < ngrp);
+    }
+    /* leftover rows [ngrp * Q1I_R, n) handled by the first lane */
+    for (int64_t r = ngrp * Q1I_R; gid == 0 && r < n; r++) {
+        if (shipdate[r] <= cutoff) {
+            const int ct = rflag[r] * 2 + lstatus[r];
+            unsigned long long tb, tp, tc, td;
+            q1i_row(tab, cents[r], disc[r], tax[r], tb, tp, tc, td);
+            const unsigned tq = qty[r];
+            #pragma unroll
+            for (int c = 0; c < NCOMBO; c++) {
+                if (ct == c) Q1_ACC_ADD(c, tb, tp, tc, td, tq, 1u);
+            }
+        }
+    }
+    q1_block_reduce(acc, lds, partials);
+}
+
 /* final cross-block merge: block (c, f) owns field f of combo c (f < 4: a
  * u128 sum, f = 4 qty, f = 5 count) and reads that word's partials with unit
  * stride across blocks. `out` is the session's device-mapped pinned block. */
@@ -402,8 +679,13 @@ extern "C" tg_status tg_q1_run(tg_session* s, const tg_tpch_lineitem_cols* cols,
     int64_t n = cols->row_count;
     /* grid sweep hook (default measured on MI355X; profiles/q1_pipelined_vs_parent.txt) */
     static int blocks_env = [] { const char* e = getenv("TG_Q1_BLOCKS"); return e ? atoi(e) : 0; }();
-    int grid = tg_grid_for(n, Q1_R);
-    if (grid > 1536) grid = 1536;
+    /* the integer forms are all set or none is (trino_gpu.h); anything else
+     * reads the f64 columns */
+    const bool ints = cols->quantity_u8 && cols->extendedprice_cents &&
+                      cols->discount_pct && cols->tax_pct;
+    int grid = tg_grid_for(n, ints ? Q1I_R : Q1_R);
+    const int cap = ints ? Q1I_GRID_CAP : 1536;
+    if (grid > cap) grid = cap;
     if (blocks_env > 0) grid = blocks_env;
     if (grid > TG_MAX_BLOCKS) grid = TG_MAX_BLOCKS;   /* partials buffer bound */
     /* the per-lane carry words and counts are 32-bit */
@@ -412,10 +694,16 @@ extern "C" tg_status tg_q1_run(tg_session* s, const tg_tpch_lineitem_cols* cols,
         return TG_ERR_INVALID_ARG;
     }
     TG_HIP_CHECK(hipEventRecord(s->ev_start, s->stream));
-    hipLaunchKernelGGL(k_q1_fused, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
-                       n, cols->shipdate, cols->quantity, cols->extendedprice,
-                       cols->discount, cols->tax, cols->returnflag, cols->linestatus,
-                       cutoff, s->q1_partials);
+    if (ints)
+        hipLaunchKernelGGL(k_q1_fused_int, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
+                           n, cols->shipdate, cols->quantity_u8, cols->extendedprice_cents,
+                           cols->discount_pct, cols->tax_pct, cols->returnflag,
+                           cols->linestatus, cutoff, s->q1_partials);
+    else
+        hipLaunchKernelGGL(k_q1_fused, dim3(grid), dim3(TG_BLOCK), 0, s->stream,
+                           n, cols->shipdate, cols->quantity, cols->extendedprice,
+                           cols->discount, cols->tax, cols->returnflag, cols->linestatus,
+                           cutoff, s->q1_partials);
     TG_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_q1_merge, dim3(NCOMBO * MERGE_FIELDS), dim3(TG_BLOCK), 0, s->stream,
                        s->q1_partials, grid, s->q1_result_dev);

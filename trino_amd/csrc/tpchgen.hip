@@ -42,7 +42,9 @@ __global__ void k_gen_lineitem(double sf, int64_t order_start, int64_t order_cou
                                int32_t* commitdate, int32_t* receiptdate,
                                int64_t* partkey, uint8_t* shipmode,
                                int64_t* tp_cents, int64_t* suppkey,
-                               uint8_t* shipinstruct)
+                               uint8_t* shipinstruct,
+                               uint8_t* quantity_u8, int32_t* extendedprice_cents,
+                               uint8_t* discount_pct, uint8_t* tax_pct)
 {
     int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_groups) return;
@@ -73,6 +75,11 @@ __global__ void k_gen_lineitem(double sf, int64_t order_start, int64_t order_cou
             if (tp_cents)      tp_cents[n] = l.tp_cents;
             if (suppkey)       suppkey[n] = l.suppkey;
             if (shipinstruct)  shipinstruct[n] = l.shipinstruct;
+            /* the integers the four f64 columns above were made from */
+            if (quantity_u8)         quantity_u8[n] = (uint8_t)l.qty;
+            if (extendedprice_cents) extendedprice_cents[n] = (int32_t)l.extprice_cents;
+            if (discount_pct)        discount_pct[n] = (uint8_t)l.discount_pct;
+            if (tax_pct)             tax_pct[n] = (uint8_t)l.tax_pct;
         }
         tpch_order_row_finished(&s);
     }
@@ -221,7 +228,9 @@ extern "C" tg_status tg_tpch_gen_lineitem(tg_session* s, double sf,
                        cols->returnflag, cols->linestatus,
                        cols->commitdate, cols->receiptdate, cols->partkey,
                        cols->shipmode, cols->tp_cents, cols->suppkey,
-                       cols->shipinstruct);
+                       cols->shipinstruct,
+                       cols->quantity_u8, cols->extendedprice_cents,
+                       cols->discount_pct, cols->tax_pct);
     TG_HIP_CHECK(hipGetLastError());
     TG_HIP_CHECK(hipStreamSynchronize(s->stream));
     TG_HIP_CHECK(hipFree(d_offsets));
@@ -260,6 +269,19 @@ extern "C" tg_status tg_tpch_lineitem_alloc(tg_session* s, double sf,
     TG_POOL_ALLOC(s, &cols->tax, rows * 8);
     TG_POOL_ALLOC(s, &cols->returnflag, rows);
     TG_POOL_ALLOC(s, &cols->linestatus, rows);
+    /* integer forms, best effort: 7 B/row on top of the 38 above. All four
+     * or none — a scale that only just fits must still generate. */
+    if (tg_pool_alloc(s, (void**)&cols->quantity_u8, (size_t)rows) != TG_OK ||
+        tg_pool_alloc(s, (void**)&cols->extendedprice_cents, (size_t)rows * 4) != TG_OK ||
+        tg_pool_alloc(s, (void**)&cols->discount_pct, (size_t)rows) != TG_OK ||
+        tg_pool_alloc(s, (void**)&cols->tax_pct, (size_t)rows) != TG_OK) {
+        tg_pool_free(s, cols->quantity_u8);
+        tg_pool_free(s, cols->extendedprice_cents);
+        tg_pool_free(s, cols->discount_pct);
+        tg_pool_free(s, cols->tax_pct);
+        cols->quantity_u8 = cols->discount_pct = cols->tax_pct = nullptr;
+        cols->extendedprice_cents = nullptr;
+    }
     return tg_tpch_gen_lineitem(s, sf, order_start, order_count, cols);
 }
 
@@ -280,6 +302,10 @@ extern "C" tg_status tg_tpch_lineitem_free(tg_session* s, tg_tpch_lineitem_cols*
     tg_pool_free(s, cols->tax);
     tg_pool_free(s, cols->returnflag);
     tg_pool_free(s, cols->linestatus);
+    tg_pool_free(s, cols->quantity_u8);
+    tg_pool_free(s, cols->extendedprice_cents);
+    tg_pool_free(s, cols->discount_pct);
+    tg_pool_free(s, cols->tax_pct);
     memset(cols, 0, sizeof(*cols));
     return TG_OK;
 }
