@@ -637,7 +637,8 @@ tg_status tg_topn_create(tg_session*,
  *
  * Out of scope: IGNORE NULLS, lag / lead defaults other than NULL, RANGE /
  * GROUPS frames with offsets, DOUBLE aggregates, VARCHAR payloads, ntile /
- * percent_rank / cume_dist, a TopNRanking cut-off. */
+ * percent_rank / cume_dist. A ranking cut-off (ranking <= N) is its own
+ * operator: tg_topn_ranking_create below. */
 typedef enum {
     TG_WIN_ROW_NUMBER = 0, TG_WIN_RANK = 1, TG_WIN_DENSE_RANK = 2,
     TG_WIN_COUNT_STAR = 3, TG_WIN_COUNT_COL = 4,
@@ -723,6 +724,61 @@ tg_status tg_window_create_ex(tg_session*,
     const int32_t* partition_channels, int32_t n_partition,
     const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
     const tg_window_spec_ex* specs, int32_t n_specs, tg_operator** out);
+
+/* ---- TopNRanking (operator/TopNRankingOperator.java): the rows whose
+ * row_number / rank / dense_rank OVER (PARTITION BY ... ORDER BY ...) is
+ * <= N, i.e. `SELECT * FROM (SELECT *, fn() OVER (...) AS r FROM t) WHERE
+ * r <= N` as one operator ----
+ * Result: exactly the page tg_window_create emits for the same types,
+ * partition channels, sort channels, sort_desc and the one ranking spec
+ * (ranking_fn, -1, FRAME_RANGE), restricted to the rows whose ranking is
+ * <= max_ranking_per_partition, the remaining rows in the same order.
+ * emit_ranking = 1: the input channels, then the BIGINT ranking channel with
+ * the same values (no validity bitmap). emit_ranking = 0: the input channels
+ * only, which is the partial step: the outputs of several such operators,
+ * fed to one operator with the same arguments, give the result of the whole
+ * input, ties in the order the outputs were fed. One output page at finish.
+ * No input rows, or only zero-row pages: no page, and `finished` is set.
+ *
+ * Row order, partition and peer equality, the handling of NULL / NaN / -0.0
+ * and "rows whose whole partition-plus-sort key ties keep input order" are
+ * the Window's (tg_window_create above), word for word.
+ *
+ * Row counts. ROW_NUMBER keeps at most N rows of a partition. RANK and
+ * DENSE_RANK keep every peer of a kept row, so a partition can emit more
+ * than N rows. n_sort == 0 makes every row of a partition a peer of every
+ * other: ROW_NUMBER then keeps the partition's first N rows in input order,
+ * RANK and DENSE_RANK keep everything. Every non-empty partition keeps at
+ * least its first row.
+ *
+ * Memory. Unlike the Window, the operator does not hold its input until
+ * finish: whenever the buffered rows reach max(T, 2 x the rows kept by the
+ * last cut) it cuts them down to the rows that can still be emitted. T is
+ * TG_TOPNR_COMPACT_ROWS (rows, >= 1) from the environment, read at create;
+ * unset: 2^24. The result does not depend on T.
+ *
+ * Rejected before anything is launched: a null session / types / out, a null
+ * array with a non-zero count, a partition / sort channel outside the
+ * channels, ranking_fn outside 0..2, max_ranking_per_partition < 1,
+ * emit_ranking outside 0..1: TG_ERR_INVALID_ARG. Any VARCHAR channel (the
+ * payload gather moves fixed-width cells, as TopN and Window):
+ * TG_ERR_UNSUPPORTED. At add_input, a page with fewer channels than declared
+ * or with cell widths that differ from `types`: TG_ERR_INVALID_ARG.
+ *
+ * Out of scope: VARCHAR channels, percent_rank / cume_dist / ntile, a
+ * hash-grouped path without a sort, spilling. */
+typedef enum {
+    TG_RANKING_ROW_NUMBER = 0, TG_RANKING_RANK = 1, TG_RANKING_DENSE_RANK = 2
+} tg_ranking_fn;
+
+tg_status tg_topn_ranking_create(tg_session*,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* partition_channels, int32_t n_partition,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    int32_t ranking_fn,                 /* tg_ranking_fn */
+    int32_t max_ranking_per_partition,  /* N >= 1 */
+    int32_t emit_ranking,               /* 1: append the BIGINT ranking channel (no bitmap); 0: rows only (the partial step) */
+    tg_operator** out);
 
 /* ---- semi join (operator/HashSemiJoinOperator.java): appends a BOOLEAN
  * matched channel to the probe page. Three-valued IN: a hit is true; a NULL

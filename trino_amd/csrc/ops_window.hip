@@ -27,10 +27,15 @@
  * lead / first_value / last_value / nth_value are one gather of the sorted
  * payload cells (k_win_value). The output channel of a value function has its
  * input channel's type.
+ *
+ * The TopNRanking operator (ranking <= N per partition) follows
+ * the Window at the end of the file and shares its boundary kernel and scan.
  */
 #include "sort_keys.h"
 #include "operators.h"
+#include <algorithm>
 #include <climits>
+#include <cstdlib>
 #include <tuple>
 
 #define WSCAN_CHUNK 1024
@@ -957,4 +962,370 @@ extern "C" tg_status tg_window_create_ex(tg_session* s,
     return window_create(s, types, n_channels, partition_channels, n_partition, sort_channels,
                          sort_desc, n_sort, specs, n_specs, TG_WIN_NTH_VALUE,
                          TG_WIN_FRAME_ROWS_BETWEEN, out);
+}
+
+/* ---- TopNRanking (operator/TopNRankingOperator.java analog):
+ * the rows of `row_number() / rank() / dense_rank() OVER (PARTITION BY ...
+ * ORDER BY ...) <= N`, without the Window's n-row payload gather and n-row
+ * ranking column. Input pages are staged; a COMPACTION orders the retained
+ * page and the staged pages together (order_pages, the retained page first,
+ * so stability keeps earlier input ahead of later input among ties), marks
+ * the boundaries (k_win_boundaries), computes the ranking with the scan the
+ * Window uses for that function (run_wscan), cuts at N (the rank cut below)
+ * and gathers ONLY the kept rows into the new retained page. add_input
+ * compacts whenever the buffered rows reach max(threshold, 2 x the rows the
+ * last compaction retained), which bounds memory by the threshold plus the
+ * kept rows and keeps the total work linear when nothing can be cut; finish
+ * compacts once more if rows were staged since, and emits the retained page
+ * with the rankings that compaction placed. Pruning is exact: a row
+ * cut over a subset of the input is cut over the whole input, and no kept
+ * row loses a row that counts towards its ranking (§6i).
+ *
+ * The rank cut is an ordered compaction in the no-waiting shape of the scan:
+ * a wave per WSCAN_CHUNK rows counts its keeps (one ballot and popcount per
+ * 64-row group), the per-chunk counts are scanned by run_wscan, and the same
+ * chunk pass runs again placing each kept row at base[chunk] + the keeps in
+ * the lanes below it. No atomics, no look-back, no flag polling; no block
+ * waits on another, so placement is deterministic and order-preserving. ---- */
+
+/* keeps of 64-row group k of a batch: rows [g + 64k, ...) below hi whose
+ * ranking is <= limit. WSCAN_BATCH groups are loaded before the first ballot,
+ * as in wscan_chunk. */
+__device__ static inline void rcut_load(const int64_t* __restrict__ ranking, int64_t g,
+                                        int64_t hi, int lane, int64_t limit,
+                                        int64_t (&rk)[WSCAN_BATCH], bool (&keep)[WSCAN_BATCH])
+{
+    #pragma unroll
+    for (int k = 0; k < WSCAN_BATCH; k++) {
+        int64_t p = g + 64 * k + lane;
+        rk[k] = p < hi ? ranking[p] : INT64_MAX;
+        keep[k] = p < hi && rk[k] <= limit;
+    }
+}
+
+/* launch 1: chunk c -> the number of its kept rows */
+__global__ void k_rcut_count(const int64_t* __restrict__ ranking, int64_t n, int64_t limit,
+                             int64_t nchunks, int64_t* __restrict__ counts)
+{
+    int64_t c = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    if (c >= nchunks) return;
+    int lane = threadIdx.x % 64;
+    int64_t lo = c * WSCAN_CHUNK, hi = min(lo + (int64_t)WSCAN_CHUNK, n);
+    int64_t kept = 0;
+    for (int64_t g = lo; g < hi; g += 64 * WSCAN_BATCH) {
+        int64_t rk[WSCAN_BATCH];
+        bool keep[WSCAN_BATCH];
+        rcut_load(ranking, g, hi, lane, limit, rk, keep);
+        #pragma unroll
+        for (int k = 0; k < WSCAN_BATCH; k++) kept += __popcll(__ballot(keep[k]));
+    }
+    if (lane == 0) counts[c] = kept;
+}
+
+/* launch 3: the chunk pass again. counts_scanned is the INCLUSIVE scan of the
+ * counts, so chunk c starts at counts_scanned[c - 1]; a kept row lands at that
+ * base + the keeps before it in its chunk. kept_rank may be null. Every write
+ * lies below counts_scanned[nchunks - 1], the size of both outputs: the keep
+ * test is the one launch 1 counted. */
+__global__ void k_rcut_place(const int64_t* __restrict__ ranking,
+                             const int64_t* __restrict__ perm, int64_t n, int64_t limit,
+                             int64_t nchunks, const int64_t* __restrict__ counts_scanned,
+                             int64_t* __restrict__ kept_idx, int64_t* __restrict__ kept_rank)
+{
+    int64_t c = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    if (c >= nchunks) return;
+    int lane = threadIdx.x % 64;
+    int64_t lo = c * WSCAN_CHUNK, hi = min(lo + (int64_t)WSCAN_CHUNK, n);
+    int64_t base = c ? counts_scanned[c - 1] : 0;
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (int64_t g = lo; g < hi; g += 64 * WSCAN_BATCH) {
+        int64_t rk[WSCAN_BATCH];
+        bool keep[WSCAN_BATCH];
+        rcut_load(ranking, g, hi, lane, limit, rk, keep);
+        #pragma unroll
+        for (int k = 0; k < WSCAN_BATCH; k++) {
+            uint64_t b = __ballot(keep[k]);
+            if (keep[k]) {
+                int64_t at = base + __popcll(b & below);
+                kept_idx[at] = perm[g + 64 * k + lane];
+                if (kept_rank) kept_rank[at] = rk[k];
+            }
+            base += __popcll(b);
+        }
+    }
+}
+
+struct TopNRankingOp : tg_operator {
+    std::vector<tg_type> types;
+    std::vector<int32_t> partition_channels;
+    std::vector<int32_t> sort_channels;
+    std::vector<int32_t> sort_desc;     /* 0 asc, 1 desc */
+    int32_t fn = TG_RANKING_ROW_NUMBER;
+    int64_t limit = 1;
+    bool emit_ranking = true;
+    int64_t threshold = 0;
+    /* after a compaction pages[0] is the retained page; the rest is staged */
+    std::vector<DevPage> pages;
+    /* with emit_ranking: the rankings of the retained page's rows, true for
+     * the input so far; finish emits them as they are when nothing was
+     * staged after the last compaction */
+    DevBlock retained_rank;
+    int64_t buffered_rows = 0;
+    int64_t staged_rows = 0;
+    int64_t last_retained = 0;
+    bool emitted = false;
+
+    tg_status add_input(const tg_page* page) override
+    {
+        TG_TRY(check_fixed_width_page("topn_ranking", page, types));
+        DevPage in;
+        TG_TRY(tg_upload_page(s, page, &in));
+        buffered_rows += in.n;
+        staged_rows += in.n;
+        pages.emplace_back(std::move(in));
+        if (buffered_rows >= std::max(threshold, 2 * last_retained)) return compact();
+        return TG_OK;
+    }
+
+    void free_rank()
+    {
+        if (retained_rank.data) tg_pool_free(s, retained_rank.data);
+        retained_rank.data = nullptr;
+    }
+
+    /* the ranking of every sorted position into d_rank, by the Window's scans */
+    tg_status ranking(PoolScratch& ws, const uint8_t* d_flags, int64_t n, int64_t* d_rank)
+    {
+        auto scan = [&](int32_t src, int32_t op, int32_t val_mask, const int64_t* vals,
+                        int64_t* out) {
+            WscanIn in{};
+            in.vals = vals;
+            in.flags = d_flags;
+            in.n = n;
+            in.head_mask = WFLAG_PARTITION;
+            in.val_mask = val_mask;
+            in.src = src;
+            in.op = op;
+            return run_wscan(s, ws, in, out);
+        };
+        if (fn == TG_RANKING_DENSE_RANK) return scan(WSRC_FLAG, WOP_ADD, WFLAG_PEER, nullptr, d_rank);
+        if (fn == TG_RANKING_ROW_NUMBER) return scan(WSRC_ONE, WOP_ADD, 0, nullptr, d_rank);
+        /* RANK: the row number of the row's first peer */
+        int64_t* d_rownum = nullptr;
+        TG_TRY(ws.alloc(&d_rownum, n * 8));
+        TG_TRY(scan(WSRC_ONE, WOP_ADD, 0, nullptr, d_rownum));
+        return scan(WSRC_MASKED, WOP_MAX, WFLAG_PEER, d_rownum, d_rank);
+    }
+
+    /* (pages) -> the page of their rows with ranking <= limit in sorted
+     * order; with rank_out also the BIGINT ranking block of those rows */
+    tg_status compact_into(PoolScratch& ws, DevPage* outp, DevBlock* rank_out)
+    {
+        const int64_t n = buffered_rows;
+        int64_t* d_perm = nullptr;
+        TG_TRY(ws.alloc(&d_perm, n * 8));
+        std::vector<std::pair<int32_t, int32_t>> keys;
+        for (int32_t ch : partition_channels) keys.emplace_back(ch, 0);
+        for (size_t j = 0; j < sort_channels.size(); j++)
+            keys.emplace_back(sort_channels[j], sort_desc[j] != 0);
+        std::vector<WinKey> host_keys;
+        TG_TRY(order_pages(s, ws, pages, n, keys, d_perm, &host_keys));
+
+        uint8_t* d_flags = nullptr;
+        WinKey* d_keytab = nullptr;
+        TG_TRY(ws.alloc(&d_flags, n));
+        TG_TRY(ws.alloc(&d_keytab, (int64_t)(host_keys.size() * sizeof(WinKey))));
+        if (!host_keys.empty()) {
+            TG_HIP_CHECK(hipMemcpyAsync(d_keytab, host_keys.data(),
+                                        host_keys.size() * sizeof(WinKey),
+                                        hipMemcpyHostToDevice, s->stream));
+            TG_HIP_CHECK(hipStreamSynchronize(s->stream));   /* host_keys is a local */
+        }
+        hipLaunchKernelGGL(k_win_boundaries, dim3(tg_grid_for(n)), dim3(TG_BLOCK), 0,
+                           s->stream, (const WinKey*)d_keytab, (int32_t)host_keys.size(),
+                           (int32_t)partition_channels.size(), (const int64_t*)d_perm, n,
+                           d_flags);
+        TG_HIP_CHECK(hipGetLastError());
+
+        int64_t* d_rank = nullptr;
+        TG_TRY(ws.alloc(&d_rank, n * 8));
+        TG_TRY(ranking(ws, d_flags, n, d_rank));
+
+        /* the rank cut: count, scan the counts, place */
+        int64_t nchunks = (n + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
+        int64_t* d_counts = nullptr;
+        uint8_t* d_noheads = nullptr;
+        TG_TRY(ws.alloc(&d_counts, nchunks * 8));
+        TG_TRY(ws.alloc(&d_noheads, nchunks));
+        int wpb = TG_BLOCK / 64;
+        dim3 grid((uint32_t)((nchunks + wpb - 1) / wpb)), block(TG_BLOCK);
+        hipLaunchKernelGGL(k_rcut_count, grid, block, 0, s->stream, (const int64_t*)d_rank, n,
+                           limit, nchunks, d_counts);
+        TG_HIP_CHECK(hipGetLastError());
+        WscanIn sum{};
+        sum.vals = d_counts;
+        sum.flags = d_noheads;      /* read, never used: head_mask is 0 */
+        sum.n = nchunks;
+        sum.src = WSRC_ARRAY;
+        sum.op = WOP_ADD;
+        TG_HIP_CHECK(hipMemsetAsync(d_noheads, 0, nchunks, s->stream));
+        TG_TRY(run_wscan(s, ws, sum, d_counts));
+        int64_t m = 0;
+        TG_HIP_CHECK(hipMemcpyAsync(&m, d_counts + (nchunks - 1), 8, hipMemcpyDeviceToHost,
+                                    s->stream));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        if (m < 1 || m > n) {     /* every partition keeps its first row */
+            TG_SET_ERR("topn_ranking: the rank cut kept %lld of %lld rows", (long long)m,
+                       (long long)n);
+            return TG_ERR_HIP;
+        }
+        int64_t* d_kept = nullptr;
+        TG_TRY(ws.alloc(&d_kept, m * 8));
+        if (rank_out) {
+            rank_out->type = TG_BIGINT;
+            rank_out->n = m;
+            TG_POOL_ALLOC(s, &rank_out->data, m * 8);
+        }
+        hipLaunchKernelGGL(k_rcut_place, grid, block, 0, s->stream, (const int64_t*)d_rank,
+                           (const int64_t*)d_perm, n, limit, nchunks,
+                           (const int64_t*)d_counts, d_kept,
+                           rank_out ? (int64_t*)rank_out->data : (int64_t*)nullptr);
+        TG_HIP_CHECK(hipGetLastError());
+
+        /* only kept rows have their payload moved */
+        TG_TRY(gather_pages(s, pages, types, d_kept, m, outp));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        return TG_OK;
+    }
+
+    /* reduce (retained page, staged pages) to one retained page */
+    tg_status compact()
+    {
+        DevPage outp;
+        DevBlock rank;
+        tg_status st;
+        {
+            PoolScratch ws(s);
+            st = compact_into(ws, &outp, emit_ranking ? &rank : nullptr);
+        }   /* the scratch is back in the pool, the stream drained */
+        if (st != TG_OK) {
+            tg_free_page(s, &outp);
+            if (rank.data) tg_pool_free(s, rank.data);
+            return st;
+        }
+        for (auto& p : pages) tg_free_page(s, &p);
+        pages.clear();
+        free_rank();
+        retained_rank = rank;
+        buffered_rows = last_retained = outp.n;
+        staged_rows = 0;
+        pages.emplace_back(std::move(outp));
+        return TG_OK;
+    }
+
+    tg_status emit()
+    {
+        /* rows staged after the last compaction: one more; otherwise the
+         * retained page and its rankings are the result already */
+        if (staged_rows) TG_TRY(compact());
+        if (buffered_rows) {
+            DevPage outp = std::move(pages[0]);
+            if (emit_ranking) {
+                outp.blocks.emplace_back(retained_rank);
+                retained_rank.data = nullptr;       /* the page owns it now */
+            }
+            stage_output(std::move(outp));
+            buffered_rows = 0;
+        }
+        for (auto& p : pages) tg_free_page(s, &p);         /* zero-row pages */
+        pages.clear();
+        return TG_OK;
+    }
+
+    tg_status get_output(tg_page* out, int* finished) override
+    {
+        if (input_finished && !emitted) {
+            emitted = true;
+            tg_status st = emit();
+            if (st != TG_OK) return st;
+        }
+        emit_staged(out, finished);
+        return TG_OK;
+    }
+
+    ~TopNRankingOp() override
+    {
+        free_rank();
+        for (auto& p : pages) tg_free_page(s, &p);
+        for (auto& p : out_pages_) tg_free_page(s, &p);
+    }
+};
+
+extern "C" tg_status tg_topn_ranking_create(tg_session* s,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* partition_channels, int32_t n_partition,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    int32_t ranking_fn, int32_t max_ranking_per_partition, int32_t emit_ranking,
+    tg_operator** out)
+{
+    if (!s || !types || !out || n_channels < 1 || n_partition < 0 || n_sort < 0 ||
+        (n_partition && !partition_channels) || (n_sort && (!sort_channels || !sort_desc))) {
+        TG_SET_ERR("invalid topn_ranking spec: null argument or negative count");
+        return TG_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n_partition; i++)
+        if (partition_channels[i] < 0 || partition_channels[i] >= n_channels) {
+            TG_SET_ERR("topn_ranking partition channel %d outside %d channels",
+                       partition_channels[i], n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+    for (int i = 0; i < n_sort; i++)
+        if (sort_channels[i] < 0 || sort_channels[i] >= n_channels) {
+            TG_SET_ERR("topn_ranking sort channel %d outside %d channels", sort_channels[i],
+                       n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+    if (ranking_fn < TG_RANKING_ROW_NUMBER || ranking_fn > TG_RANKING_DENSE_RANK) {
+        TG_SET_ERR("topn_ranking: unknown ranking function %d", ranking_fn);
+        return TG_ERR_INVALID_ARG;
+    }
+    if (max_ranking_per_partition < 1) {
+        TG_SET_ERR("topn_ranking: max ranking %d, at least 1 required",
+                   max_ranking_per_partition);
+        return TG_ERR_INVALID_ARG;
+    }
+    if (emit_ranking < 0 || emit_ranking > 1) {
+        TG_SET_ERR("topn_ranking: emit_ranking %d, 0 or 1 expected", emit_ranking);
+        return TG_ERR_INVALID_ARG;
+    }
+    /* the payload gather moves fixed-width cells only (as TopN and Window) */
+    for (int i = 0; i < n_channels; i++)
+        if (types[i] == TG_VARCHAR) {
+            TG_SET_ERR("topn_ranking: VARCHAR channel %d is not supported", i);
+            return TG_ERR_UNSUPPORTED;
+        }
+    auto* op = new TopNRankingOp();
+    op->s = s;
+    for (int i = 0; i < n_channels; i++) op->types.push_back((tg_type)types[i]);
+    op->partition_channels.assign(partition_channels, partition_channels + n_partition);
+    op->sort_channels.assign(sort_channels, sort_channels + n_sort);
+    op->sort_desc.assign(sort_desc, sort_desc + n_sort);
+    op->fn = ranking_fn;
+    op->limit = max_ranking_per_partition;
+    op->emit_ranking = emit_ranking != 0;
+    /* buffered rows that trigger a compaction; read here, once per operator.
+     * MI355X, 2^24 rows of three BIGINT channels in 16 pages, ROW_NUMBER,
+     * N = 10, median ms end to end (profiles/topn_ranking_cost.txt):
+     *     threshold   ~2^20 partitions   one partition
+     *     2^20             10.623            12.315
+     *     2^22              9.150             5.829
+     *     2^24              5.718             4.498
+     * Every compaction is a sort of what is buffered, so the fewest
+     * compactions win; the fastest of the three is kept. It is also the
+     * memory bound: 2^24 rows of the input's channels stay buffered. */
+    const char* e = getenv("TG_TOPNR_COMPACT_ROWS");
+    int64_t rows = e ? atoll(e) : 0;
+    op->threshold = rows >= 1 ? rows : ((int64_t)1 << 24);
+    *out = op;
+    return TG_OK;
 }

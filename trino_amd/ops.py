@@ -549,6 +549,40 @@ def window_ex(session, types, partition_channels, sort_channels, sort_desc, spec
     return op
 
 
+RANKING_ROW_NUMBER, RANKING_RANK, RANKING_DENSE_RANK = range(3)
+
+_lib.tg_topn_ranking_create.restype = ctypes.c_int
+_lib.tg_topn_ranking_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_void_p]
+
+
+def topn_ranking(session, types, partition_channels, sort_channels, sort_desc, ranking_fn,
+                 max_rank, emit_ranking=True):
+    """TopNRanking operator (operator/TopNRankingOperator analog): the rows
+    whose RANKING_* function OVER (PARTITION BY ... ORDER BY ...) is <=
+    max_rank, in the Window operator's row order. The one output page holds
+    the input channels and, with emit_ranking, the BIGINT ranking channel;
+    emit_ranking=False is the partial step, whose output feeds another
+    topn_ranking. TG_TOPNR_COMPACT_ROWS in the environment at this call sets
+    the buffered rows that trigger a cut."""
+    h = ctypes.c_void_p()
+    ty = _i32arr(types)
+    pc = _i32arr(partition_channels)
+    sc = _i32arr(sort_channels)
+    sd = _i32arr(sort_desc)
+    _check(_lib.tg_topn_ranking_create(
+        session._h, ty.ctypes.data, len(ty),
+        pc.ctypes.data if len(pc) else None, len(pc),
+        sc.ctypes.data if len(sc) else None, sd.ctypes.data if len(sd) else None, len(sc),
+        ranking_fn, max_rank, 1 if emit_ranking else 0, ctypes.byref(h)))
+    op = Operator(session, h)
+    op._keep = (ty, pc, sc, sd)
+    return op
+
+
 def join_key_range(bridge):
     """Dynamic filter source: (min, max, non_null_rows) of the build keys."""
     mn = ctypes.c_int64()
