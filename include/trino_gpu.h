@@ -101,12 +101,33 @@ void      tg_session_close(tg_session*);
  * bitmap even over NULL-free inputs. Integer overflow is undefined. AND / OR /
  * NOT / BETWEEN are Kleene logic; a filter keeps a row iff the result is
  * non-NULL and non-zero.
- * Validation (host side, before anything is launched): a program must reduce
+ * NULL handling: TG_EXPR_IS_NULL, TG_EXPR_COALESCE and TG_EXPR_CONST_NULL test,
+ * replace and produce NULL; TG_EXPR_SELECT is the two-armed conditional that
+ * CASE / IF / NULLIF are written with (both arms are evaluated: the IR has no
+ * per-row error). Operand order of SELECT is otherwise, cond, then, so a
+ * searched CASE with n WHENs is `else, cN, vN, SELECT, ..., c1, v1, SELECT`
+ * at a depth of 3 plus its deepest operand, whatever n is. IF(c, a, b) is
+ * `b, c, a, SELECT`; NULLIF(a, b) is `a, a, b, EQ, NULL, SELECT`.
+ * Lanes: the lane (int64 or double) of every stack value depends only on the
+ * program and the page's column types, never on the row: a NULL cell keeps
+ * its column's lane. SELECT and COALESCE give an int64 result iff both value
+ * operands are int64; otherwise an int64 operand is converted as (double)i.
+ * Set membership: TG_EXPR_IN_LIST with arg0 = k is followed by k
+ * TG_EXPR_IN_ITEM instructions, one BIGINT item each in imm.i64 (duplicates
+ * and any order allowed; 1 <= k <= 4096). The result is NULL for a NULL
+ * operand, else 1 / 0. An int64 operand compares exactly; a double operand d
+ * compares as d == (double)item, so NaN gives 0. A NULL item has no encoding:
+ * `x IN (1, NULL)` is `IN_LIST ... CONST_NULL OR`; NOT IN is `IN_LIST ... NOT`.
+ * Validation (host side, before anything is launched; tg_expr_check below
+ * runs the create-time part without a session): a program must reduce
  * to one value (else TG_ERR_INVALID_ARG) within 6 stack slots and use only
- * the opcodes 0..16 (else TG_ERR_UNSUPPORTED: TG_EXPR_IN_I64 is reserved, not
- * implemented); when a page arrives, every TG_EXPR_COL index must lie inside
- * its channels (TG_ERR_INVALID_ARG), and a VARCHAR channel may only be named
- * by a one-instruction identity projection (TG_ERR_UNSUPPORTED otherwise). */
+ * the opcodes 0..16 and 32..37 (else TG_ERR_UNSUPPORTED; more than 4096 items
+ * in one list also); an IN_LIST with k < 1, with fewer than k IN_ITEMs after
+ * it, an IN_ITEM anywhere else, and a CONST_NULL arg0 outside {0, 1} are
+ * TG_ERR_INVALID_ARG. When a page arrives, every TG_EXPR_COL index must lie
+ * inside its channels (TG_ERR_INVALID_ARG), and a VARCHAR channel may only be
+ * named by a one-instruction identity projection (TG_ERR_UNSUPPORTED
+ * otherwise). */
 typedef enum {
     TG_EXPR_COL = 0,       /* push column[arg0] value */
     TG_EXPR_CONST_F64 = 1, /* push f64 constant */
@@ -117,7 +138,18 @@ typedef enum {
     TG_EXPR_EQ = 11, TG_EXPR_NE = 12,
     TG_EXPR_AND = 13, TG_EXPR_OR = 14, TG_EXPR_NOT = 15,
     TG_EXPR_BETWEEN = 16,  /* value, lo, hi on stack */
-    TG_EXPR_IN_I64 = 17    /* reserved: rejected with TG_ERR_UNSUPPORTED */
+    TG_EXPR_IN_I64 = 17,   /* reserved and unimplemented (as 18..31): rejected
+                              with TG_ERR_UNSUPPORTED. The working form of IN
+                              is TG_EXPR_IN_LIST */
+    TG_EXPR_IS_NULL = 32,  /* pop a; push 1 if a is NULL else 0 (never NULL) */
+    TG_EXPR_SELECT = 33,   /* otherwise, cond, then on stack; `then` if cond is
+                              non-NULL and non-zero, else `otherwise` */
+    TG_EXPR_COALESCE = 34, /* a, b on stack; a if a is non-NULL, else b */
+    TG_EXPR_CONST_NULL = 35, /* push NULL; arg0 = 0 int64 lane, 1 double lane */
+    TG_EXPR_IN_LIST = 36,  /* pop a; arg0 = k, the next k instructions are
+                              TG_EXPR_IN_ITEM; push a IN (items) */
+    TG_EXPR_IN_ITEM = 37   /* one BIGINT item of the preceding IN_LIST in
+                              imm.i64; no stack effect */
 } tg_expr_op;
 
 typedef struct tg_expr_inst {
@@ -127,6 +159,18 @@ typedef struct tg_expr_inst {
 } tg_expr_inst;
 
 typedef struct tg_expr { const tg_expr_inst* insts; int32_t count; } tg_expr;
+
+/* The create-time validation of a program, on the host alone: needs no
+ * session and no GPU. Returns the status, and leaves in tg_last_error the
+ * text, that tg_filter_run / tg_filter_project_create give for the program. */
+tg_status tg_expr_check(const tg_expr* e);
+/* The representation a compiled program gives an IN list with these items,
+ * host only: 0 = one 64-bit mask (max - min < 64), 1 = a bitmap (max - min <
+ * 4096), 2 = a sorted array; -1 for no items. Only a list that directly
+ * follows a TG_EXPR_COL of an integer column is tested through it (the
+ * conjunction kernel); everywhere else the interpreter searches the sorted
+ * items inside the program. */
+int32_t tg_expr_in_form(const int64_t* items, int32_t n);
 
 /* ---- generic operator handle (operator/Operator.java:18-50) ---- */
 typedef struct tg_operator tg_operator;

@@ -61,15 +61,10 @@ def main(sf=100.0):
                                           (p_sz.value, ops.TG_INTEGER)],
                                          part_count))
         sizes = [49, 14, 23, 45, 19, 3, 36, 9]
-        in_chain = []
-        for i, v in enumerate(sizes):
-            in_chain += [("col", 3), ("i64", v), "eq"]
-            if i:
-                in_chain.append("or")
-        fexpr = ops.expr(*(in_chain +
-                           [("col", 1), ("i64", 45), "ne", "and",
-                            ("col", 2), ("i64", 65), ("i64", 69), "between",
-                            "not", "and"]))
+        fexpr = ops.expr(("col", 3), ("in", sizes),
+                         ("col", 1), ("i64", 45), "ne", "and",
+                         ("col", 2), ("i64", 65), ("i64", 69), "between",
+                         "not", "and")
         fp = ops.filter_project(s, fexpr,
                                 [ops.expr(("col", 0)), ops.expr(("col", 1)),
                                  ops.expr(("col", 2)), ops.expr(("col", 3))],

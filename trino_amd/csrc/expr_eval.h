@@ -10,6 +10,7 @@
 struct KCol { const void* data; const uint64_t* valid; int32_t type; int32_t _pad; };
 
 constexpr int EXPR_STACK_SLOTS = 6;   /* s0..s5 of eval_expr_cols */
+constexpr int IN_LIST_MAX = 4096;     /* items of one TG_EXPR_IN_LIST */
 
 /* Typed stack value: BIGINT/INTEGER/DATE/… stay in an exact int64 lane
  * (mirrors sql/gen/columnar/CallColumnarFilterGenerator.java:160-198 which
@@ -23,7 +24,9 @@ __device__ static inline TVal load_tcol(const KCol& c, int64_t i)
 {
     TVal v;
     v.null = c.valid && !((c.valid[i >> 6] >> (i & 63)) & 1);
-    if (v.null) { v.f = 0.0; v.i = 0; v.isint = true; return v; }
+    /* a NULL cell keeps its column's lane: SELECT / COALESCE can put a value
+     * in its place, and the lane of that result must not depend on the row */
+    if (v.null) { v.f = 0.0; v.i = 0; v.isint = c.type != TG_DOUBLE; return v; }
     switch (c.type) {
         case TG_BIGINT: v.i = ((const int64_t*)c.data)[i]; v.isint = true; v.f = (double)v.i; break;
         case TG_INTEGER: case TG_DATE: v.i = ((const int32_t*)c.data)[i]; v.isint = true; v.f = (double)v.i; break;
@@ -60,7 +63,11 @@ struct PairCols {           /* c < n_probe: probe row cell, else build row cell 
  * follow SQL Kleene three-valued logic (io.trino.sql.ir.Logical semantics:
  * AND — false dominates null; OR — true dominates null; NOT null = null),
  * so compositions under NOT are correct; a null FILTER result rejects the
- * row at the call site (CallColumnarFilterGenerator's nullable loop). */
+ * row at the call site (CallColumnarFilterGenerator's nullable loop).
+ * SELECT / COALESCE pick one of two evaluated operands; their lane is int64
+ * iff both value operands are (TVal::f mirrors every int64 value, so the
+ * double lane reads .f of either). IN_LIST searches the items that follow it
+ * in `prog` (sorted and de-duplicated by tg_compile_expr) and skips them. */
 template <typename Cols>
 __device__ static TVal eval_expr_cols(const tg_expr_inst* prog, int count, const Cols& col)
 {
@@ -83,8 +90,8 @@ __device__ static TVal eval_expr_cols(const tg_expr_inst* prog, int count, const
                                   : (a.f op_ b.f ? 1 : 0); \
         r.f = (double)r.i; PUSH(r); } while (0)
 
-    for (int k = 0; k < count; k++) {
-        tg_expr_inst in = prog[k];
+    for (int pc = 0; pc < count; pc++) {
+        tg_expr_inst in = prog[pc];
         TVal a, b, c;
         switch (in.op) {
             case TG_EXPR_COL: PUSH(col(in.arg0)); break;
@@ -141,6 +148,48 @@ __device__ static TVal eval_expr_cols(const tg_expr_inst* prog, int count, const
                 r.i = (!r.null && !af && !bf) ? 1 : 0;
                 r.f = (double)r.i; PUSH(r); break;
             }
+            case TG_EXPR_IS_NULL: { POP(a);
+                TVal r; r.isint = true; r.null = false;
+                r.i = a.null ? 1 : 0;
+                r.f = (double)r.i; PUSH(r); break;
+            }
+            case TG_EXPR_SELECT: { POP(c); POP(b); POP(a);   /* otherwise, cond, then */
+                bool take = !b.null && tval_truthy(b);
+                TVal r; r.isint = a.isint & c.isint;
+                r.null = take ? c.null : a.null;
+                r.f = take ? c.f : a.f;
+                r.i = r.isint ? (take ? c.i : a.i) : 0;
+                PUSH(r); break;
+            }
+            case TG_EXPR_COALESCE: { POP(b); POP(a);
+                TVal r; r.isint = a.isint & b.isint;
+                r.null = a.null & b.null;
+                r.f = a.null ? b.f : a.f;
+                r.i = r.isint ? (a.null ? b.i : a.i) : 0;
+                PUSH(r); break;
+            }
+            case TG_EXPR_CONST_NULL: { TVal v; v.f = 0.0; v.i = 0; v.isint = in.arg0 == 0; v.null = true; PUSH(v); break; }
+            case TG_EXPR_IN_LIST: { POP(a);
+                /* branch-free search for the last item <= a over the sorted,
+                 * distinct items inline in prog (16-byte stride); the trip
+                 * count depends on the list alone, so the wave stays converged.
+                 * (double)item is monotone over sorted items, and every
+                 * compare with NaN is false: NaN IN (...) is 0 */
+                const tg_expr_inst* base = prog + pc + 1;
+                for (int len = in.arg0; len > 1;) {
+                    int half = len >> 1;
+                    bool le = a.isint ? base[half].imm.i64 <= a.i
+                                      : (double)base[half].imm.i64 <= a.f;
+                    base += le ? half : 0;
+                    len -= half;
+                }
+                bool found = a.isint ? base->imm.i64 == a.i : (double)base->imm.i64 == a.f;
+                TVal r; r.isint = true; r.null = a.null;
+                r.i = (!a.null && found) ? 1 : 0;
+                r.f = (double)r.i; PUSH(r);
+                pc += in.arg0;      /* the items */
+                break;
+            }
             default: break;
         }
     }
@@ -160,7 +209,8 @@ __device__ static inline TVal eval_expr(const tg_expr_inst* prog, int count,
 }
 
 /* host-side program checks shared by every operator that takes a tg_expr
- * (ops_filter.hip): opcodes 0..16 (else TG_ERR_UNSUPPORTED), no underflow and
- * one value left (else TG_ERR_INVALID_ARG), at most EXPR_STACK_SLOTS slots (else
- * `too_deep`) */
+ * (ops_filter.hip): opcodes 0..16 and 32..37 and at most IN_LIST_MAX items per
+ * list (else TG_ERR_UNSUPPORTED), well-formed IN lists and CONST_NULL lanes, no
+ * underflow and one value left (else TG_ERR_INVALID_ARG), at most
+ * EXPR_STACK_SLOTS slots (else `too_deep`) */
 tg_status check_expr_depth(const tg_expr* e, tg_status too_deep = TG_ERR_UNSUPPORTED);

@@ -148,10 +148,37 @@ struct tg_operator {
 };
 
 /* expression IR (host-compiled to a device-constant program) */
+/* one TG_EXPR_IN_LIST of a compiled program. tg_compile_expr sorts and
+ * de-duplicates the items in place (host and device copy alike), and picks
+ * the representation k_filter_terms tests when the list is a term `COL IN`: */
+enum InForm {
+    IN_FORM_MASK = 0,     /* span <= 64: one 64-bit mask, bit (v - min) */
+    IN_FORM_BITMAP = 1,   /* span <= IN_BITMAP_BITS: device bitmap, bit (v - min) */
+    IN_FORM_SEARCH = 2    /* otherwise: sorted device array, lower-bound search */
+};
+#define IN_BITMAP_BITS 4096
+struct InSet {
+    int pos = 0;                  /* index of the IN_LIST instruction */
+    int n = 0;                    /* distinct items */
+    int64_t mn = 0, mx = 0;
+    InForm form = IN_FORM_MASK;
+    uint64_t mask = 0;            /* IN_FORM_MASK */
+    uint64_t* d_bitmap = nullptr; /* IN_FORM_BITMAP: (span + 63) / 64 words, owned */
+    int64_t* d_sorted = nullptr;  /* IN_FORM_SEARCH: n items, owned */
+};
+/* the representation of a sorted list of distinct items; max - min + 1 never
+ * leaves uint64 (a list may hold INT64_MIN and INT64_MAX) */
+inline InForm in_form_for(int64_t mn, int64_t mx)
+{
+    uint64_t span_m1 = (uint64_t)mx - (uint64_t)mn;
+    return span_m1 < 64 ? IN_FORM_MASK : span_m1 < IN_BITMAP_BITS ? IN_FORM_BITMAP : IN_FORM_SEARCH;
+}
+
 struct ExprProgram {
     std::vector<tg_expr_inst> insts;
     tg_expr_inst* d_insts = nullptr;   /* device copy */
     int count = 0;
+    std::vector<InSet> sets;           /* in program order */
 };
 tg_status tg_compile_expr(tg_session* s, const tg_expr* e, ExprProgram* out);
 void tg_free_expr(tg_session* s, ExprProgram* p);

@@ -1,6 +1,7 @@
 /* ops_core.hip — page upload/decode, expression compile, generic operator
  * C-ABI glue (operator/Operator.java:18-50 surface). */
 #include "operators.h"
+#include <algorithm>
 
 /* ---- dictionary / RLE decode kernels (collapse to flat values on upload;
  * DictionaryBlock.java:55-58, RunLengthEncodedBlock) ---- */
@@ -203,11 +204,70 @@ void tg_free_page(tg_session* s, DevPage* p)
     p->n = 0;
 }
 
+/* Copies a validated program (check_expr_depth), rewriting every IN list to
+ * its sorted, distinct items: the interpreter searches them where they sit in
+ * the program, so host and device copy are the same. A list that directly
+ * follows a TG_EXPR_COL can become a term of k_filter_terms; for those the
+ * bitmap or the sorted array of its form is uploaded here and owned by `out`. */
 tg_status tg_compile_expr(tg_session* s, const tg_expr* e, ExprProgram* out)
 {
-    out->insts.assign(e->insts, e->insts + e->count);
-    out->count = e->count;
-    if (out->count > 128) { TG_SET_ERR("expression too long (>128 insts)"); return TG_ERR_UNSUPPORTED; }
+    out->insts.clear();
+    out->sets.clear();
+    out->insts.reserve(e->count);
+    int n_ops = 0;
+    for (int i = 0; i < e->count; i++) {
+        const tg_expr_inst& in = e->insts[i];
+        n_ops++;
+        if (in.op != TG_EXPR_IN_LIST) { out->insts.push_back(in); continue; }
+        std::vector<int64_t> items(in.arg0);
+        for (int j = 0; j < in.arg0; j++) items[j] = e->insts[i + 1 + j].imm.i64;
+        std::sort(items.begin(), items.end());
+        items.erase(std::unique(items.begin(), items.end()), items.end());
+        InSet set;
+        set.pos = (int)out->insts.size();
+        set.n = (int)items.size();
+        set.mn = items.front();
+        set.mx = items.back();
+        set.form = in_form_for(set.mn, set.mx);
+        tg_expr_inst head = in;
+        head.arg0 = set.n;
+        out->insts.push_back(head);
+        for (int64_t v : items) {
+            tg_expr_inst it{};
+            it.op = TG_EXPR_IN_ITEM;
+            it.imm.i64 = v;
+            out->insts.push_back(it);
+        }
+        bool term = i > 0 && e->insts[i - 1].op == TG_EXPR_COL;
+        if (set.form == IN_FORM_MASK) {
+            for (int64_t v : items) set.mask |= 1ull << ((uint64_t)v - (uint64_t)set.mn);
+        }
+        else if (term && set.form == IN_FORM_BITMAP) {
+            std::vector<uint64_t> bm(((uint64_t)set.mx - (uint64_t)set.mn) / 64 + 1, 0);
+            for (int64_t v : items) {
+                uint64_t b = (uint64_t)v - (uint64_t)set.mn;
+                bm[b >> 6] |= 1ull << (b & 63);
+            }
+            tg_status st = upload_flat(s, bm.data(), 0, (int64_t)bm.size() * 8, (void**)&set.d_bitmap);
+            if (st == TG_OK && hipStreamSynchronize(s->stream) != hipSuccess) st = TG_ERR_HIP;
+            if (st != TG_OK) { out->sets.push_back(set); tg_free_expr(s, out); return st; }
+        }
+        else if (term) {
+            tg_status st = upload_flat(s, items.data(), 0, (int64_t)items.size() * 8, (void**)&set.d_sorted);
+            /* the source is a local: the copy ends before it goes away */
+            if (st == TG_OK && hipStreamSynchronize(s->stream) != hipSuccess) st = TG_ERR_HIP;
+            if (st != TG_OK) { out->sets.push_back(set); tg_free_expr(s, out); return st; }
+        }
+        out->sets.push_back(set);
+        i += in.arg0;
+    }
+    out->count = (int)out->insts.size();
+    /* an item is data, not an operation: the length limit counts the rest */
+    if (n_ops > 128) {
+        TG_SET_ERR("expression too long (>128 insts)");
+        tg_free_expr(s, out);
+        return TG_ERR_UNSUPPORTED;
+    }
     TG_POOL_ALLOC(s, &out->d_insts, out->count * sizeof(tg_expr_inst));
     TG_HIP_CHECK(hipMemcpyAsync(out->d_insts, out->insts.data(),
                                 out->count * sizeof(tg_expr_inst),
@@ -216,10 +276,23 @@ tg_status tg_compile_expr(tg_session* s, const tg_expr* e, ExprProgram* out)
     return TG_OK;
 }
 
+extern "C" int32_t tg_expr_in_form(const int64_t* items, int32_t n)
+{
+    if (!items || n < 1) return -1;
+    return (int32_t)in_form_for(*std::min_element(items, items + n),
+                                *std::max_element(items, items + n));
+}
+
 void tg_free_expr(tg_session* s, ExprProgram* p)
 {
     if (p->d_insts) tg_pool_free(s, p->d_insts);
     p->d_insts = nullptr;
+    for (auto& set : p->sets) {
+        if (set.d_bitmap) tg_pool_free(s, set.d_bitmap);
+        if (set.d_sorted) tg_pool_free(s, set.d_sorted);
+        set.d_bitmap = nullptr;
+        set.d_sorted = nullptr;
+    }
 }
 
 /* ---- generic operator C ABI ---- */

@@ -96,12 +96,19 @@ __global__ void k_filter_cmp(KCol col, int op, double cval, int64_t icval, int i
 #define FTERM_MAX 8
 struct FTerm {
     int32_t kind;     /* 0 = colA cmp const, 1 = colA cmp colB,
-                         2 = colA between [c1,c2], 3 = colA in {c1,c2} */
-    int32_t colA, colB, op;
+                         2 = colA between [c1,c2], 3 = colA in {c1,c2},
+                         4 = integer colA in set, 5 = colA not between [c1,c2] */
+    int32_t colA, colB, op;   /* kind 4: op is the set's InForm */
     double c1, c2;
-    int64_t i1, i2;   /* exact int64 views of c1/c2 when int_mode */
+    int64_t i1, i2;   /* exact int64 views of c1/c2 when int_mode;
+                         kind 4: min and max of the set */
     int32_t int_mode; /* colA is an integer type and consts were CONST_I64 */
-    int32_t _pad;
+    int32_t set_n;    /* kind 4, IN_FORM_SEARCH: items in set.sorted */
+    union {           /* kind 4: the set, by form */
+        uint64_t mask;            /* bit (v - i1), no memory access per row */
+        const uint64_t* bitmap;   /* bit (v - i1) of an ExprProgram's bitmap */
+        const int64_t* sorted;    /* an ExprProgram's sorted distinct items */
+    } set;
 };
 struct FTerms { FTerm t[FTERM_MAX]; int n; };
 
@@ -154,6 +161,31 @@ __global__ void k_filter_terms(FTerms ft, const KCol* __restrict__ cols,
                 }
                 case 2: pass = !a.null && (f.int_mode ? (a.i >= f.i1 && a.i <= f.i2)
                                                       : (a.f >= f.c1 && a.f <= f.c2)); break;
+                case 4: {
+                    /* d wraps to a huge value below the minimum, so one
+                     * unsigned compare is the range test of every form and
+                     * keeps the bitmap read inside its (span + 63) / 64 words */
+                    uint64_t d = (uint64_t)a.i - (uint64_t)f.i1;
+                    bool in = d <= (uint64_t)f.i2 - (uint64_t)f.i1;
+                    if (f.op == IN_FORM_MASK)
+                        in = in && ((f.set.mask >> (d & 63)) & 1);
+                    else if (f.op == IN_FORM_BITMAP)
+                        in = in && ((f.set.bitmap[d >> 6] >> (d & 63)) & 1);
+                    else {
+                        /* last item <= a.i; log2(set_n) steps for every lane */
+                        const int64_t* base = f.set.sorted;
+                        for (int len = f.set_n; len > 1;) {
+                            int half = len >> 1;
+                            base += (base[half] <= a.i) ? half : 0;
+                            len -= half;
+                        }
+                        in = *base == a.i;
+                    }
+                    pass = !a.null && in;
+                    break;
+                }
+                case 5: pass = !a.null && !(f.int_mode ? (a.i >= f.i1 && a.i <= f.i2)
+                                                       : (a.f >= f.c1 && a.f <= f.c2)); break;
                 default: pass = !a.null && (f.int_mode ? (a.i == f.i1 || a.i == f.i2)
                                                        : (a.f == f.c1 || a.f == f.c2)); break;
             }
@@ -187,6 +219,21 @@ static int parse_fterms(const ExprProgram& pred, const std::vector<KCol>& cols, 
         FTerm& f = out->t[nt];
         bool i1 = false, i2 = false;
         bool col_int = type_is_int(cols[I[p].arg0].type);
+        /* IN set: COL IN_LIST ITEM*k over an integer column (a DOUBLE column
+         * compares against (double)item: the interpreter does that) */
+        if (p + 1 < N && I[p + 1].op == TG_EXPR_IN_LIST) {
+            const InSet* set = nullptr;
+            for (const InSet& c : pred.sets) if (c.pos == p + 1) set = &c;
+            if (!set || !col_int) return false;
+            if (set->form != IN_FORM_MASK && !set->d_bitmap && !set->d_sorted) return false;
+            f.kind = 4; f.colA = I[p].arg0; f.colB = -1; f.op = set->form;
+            f.c1 = f.c2 = 0; f.i1 = set->mn; f.i2 = set->mx; f.int_mode = 1;
+            f.set_n = set->n;
+            if (set->form == IN_FORM_MASK) f.set.mask = set->mask;
+            else if (set->form == IN_FORM_BITMAP) f.set.bitmap = set->d_bitmap;
+            else f.set.sorted = set->d_sorted;
+            p += 2 + set->n; nt++; return true;
+        }
         /* IN-pair: COL C EQ COL C EQ OR (same column) */
         if (p + 6 < N && cval(I[p + 1], &f.c1, &f.i1, &i1) && I[p + 2].op == TG_EXPR_EQ &&
             I[p + 3].op == TG_EXPR_COL && I[p + 3].arg0 == I[p].arg0 &&
@@ -202,7 +249,11 @@ static int parse_fterms(const ExprProgram& pred, const std::vector<KCol>& cols, 
             I[p + 3].op == TG_EXPR_BETWEEN) {
             f.kind = 2; f.colA = I[p].arg0; f.colB = -1; f.op = 0;
             f.int_mode = col_int && i1 && i2;
-            p += 4; nt++; return true;
+            p += 4; nt++;
+            /* COL C C BETWEEN NOT: over constants the Kleene NOT of a
+             * non-NULL BETWEEN is its plain negation */
+            if (p < N && I[p].op == TG_EXPR_NOT) { f.kind = 5; p++; }
+            return true;
         }
         /* COL cmp CONST */
         if (p + 2 < N && cval(I[p + 1], &f.c1, &f.i1, &i1) && is_cmp(I[p + 2].op)) {
@@ -809,12 +860,12 @@ __global__ void k_proj_cmp_flag(KCol col, int op, double cval, int64_t icval,
     }
 }
 
-/* an integer `/ 0` yields NULL, so a program with a DIV needs an output
- * bitmap even over NULL-free inputs */
-static bool expr_has_div(const ExprProgram& e)
+/* an integer `/ 0` yields NULL and CONST_NULL is one, so a program with
+ * either needs an output bitmap even over NULL-free inputs */
+static bool expr_makes_null(const ExprProgram& e)
 {
     for (int i = 0; i < e.count; i++)
-        if (e.insts[i].op == TG_EXPR_DIV) return true;
+        if (e.insts[i].op == TG_EXPR_DIV || e.insts[i].op == TG_EXPR_CONST_NULL) return true;
     return false;
 }
 
@@ -874,7 +925,7 @@ tg_status run_project(tg_session* s, const ExprProgram& proj, tg_type out_type,
     }
 
     std::vector<KCol> cols(page.blocks.size());
-    bool any_null = expr_has_div(proj);
+    bool any_null = expr_makes_null(proj);
     for (size_t i = 0; i < page.blocks.size(); i++) {
         cols[i] = {page.blocks[i].data, page.blocks[i].valid, (int32_t)page.blocks[i].type, 0};
         any_null |= page.blocks[i].valid != nullptr;
@@ -1041,7 +1092,7 @@ struct FilterProjectOp : tg_operator {
         std::vector<KProj> kp(projections.size());
         bool any_null = false;
         for (auto& b : in.blocks) any_null |= b.valid != nullptr;
-        for (auto& p : projections) any_null |= expr_has_div(p);
+        for (auto& p : projections) any_null |= expr_makes_null(p);
         for (size_t p = 0; p < projections.size(); p++) {
             DevBlock& ob = outp.blocks[p];
             bool ident = projections[p].count == 1 &&
@@ -1095,10 +1146,14 @@ tg_status check_expr_depth(const tg_expr* e, tg_status too_deep)
 {
     int sp = 0, maxsp = 0;
     if (!e->insts || e->count < 1) { TG_SET_ERR("empty expr"); return TG_ERR_INVALID_ARG; }
+    int n_ops = 0;
     for (int i = 0; i < e->count; i++) {
         int op = e->insts[i].op;
-        /* TG_EXPR_IN_I64 is declared in the header but not implemented */
-        if (op < TG_EXPR_COL || op > TG_EXPR_BETWEEN) {
+        n_ops++;
+        /* 17..31 stay unimplemented: TG_EXPR_IN_I64 is reserved, TG_EXPR_IN_LIST
+         * is the working form */
+        if (op < TG_EXPR_COL || (op > TG_EXPR_BETWEEN && op < TG_EXPR_IS_NULL) ||
+            op > TG_EXPR_IN_ITEM) {
             TG_SET_ERR("expr opcode %d at inst %d is not implemented", op, i);
             return TG_ERR_UNSUPPORTED;
         }
@@ -1106,18 +1161,58 @@ tg_status check_expr_depth(const tg_expr* e, tg_status too_deep)
             TG_SET_ERR("expr column index %d at inst %d", e->insts[i].arg0, i);
             return TG_ERR_INVALID_ARG;
         }
-        switch (e->insts[i].op) {
-            case TG_EXPR_COL: case TG_EXPR_CONST_F64: case TG_EXPR_CONST_I64: sp++; break;
-            case TG_EXPR_NOT: break;
-            case TG_EXPR_BETWEEN: sp -= 2; break;
+        if (op == TG_EXPR_CONST_NULL && (e->insts[i].arg0 < 0 || e->insts[i].arg0 > 1)) {
+            TG_SET_ERR("expr NULL literal lane %d at inst %d (0 = integer, 1 = double)",
+                       e->insts[i].arg0, i);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (op == TG_EXPR_IN_ITEM) {
+            TG_SET_ERR("expr IN item at inst %d outside an IN list", i);
+            return TG_ERR_INVALID_ARG;
+        }
+        if (op == TG_EXPR_IN_LIST) {
+            int32_t k = e->insts[i].arg0;
+            if (k < 1) {
+                TG_SET_ERR("expr IN list of %d items at inst %d", k, i);
+                return TG_ERR_INVALID_ARG;
+            }
+            if (k > IN_LIST_MAX) {
+                TG_SET_ERR("expr IN list of %d items at inst %d > %d", k, i, IN_LIST_MAX);
+                return TG_ERR_UNSUPPORTED;
+            }
+            if (k > e->count - 1 - i) {
+                TG_SET_ERR("expr IN list of %d items at inst %d runs past the program", k, i);
+                return TG_ERR_INVALID_ARG;
+            }
+            for (int j = 1; j <= k; j++)
+                if (e->insts[i + j].op != TG_EXPR_IN_ITEM) {
+                    TG_SET_ERR("expr inst %d is not an IN item (IN list of %d items at inst %d)",
+                               i + j, k, i);
+                    return TG_ERR_INVALID_ARG;
+                }
+        }
+        switch (op) {
+            case TG_EXPR_COL: case TG_EXPR_CONST_F64: case TG_EXPR_CONST_I64:
+            case TG_EXPR_CONST_NULL: sp++; break;
+            case TG_EXPR_NOT: case TG_EXPR_IS_NULL: case TG_EXPR_IN_LIST: break;
+            case TG_EXPR_BETWEEN: case TG_EXPR_SELECT: sp -= 2; break;
             default: sp -= 1; break;
         }
         if (sp > maxsp) maxsp = sp;
         if (sp < 1) { TG_SET_ERR("expr stack underflow at inst %d", i); return TG_ERR_INVALID_ARG; }
+        if (op == TG_EXPR_IN_LIST) i += e->insts[i].arg0;   /* the items are data */
     }
     if (maxsp > MAX_STACK) { TG_SET_ERR("expr stack depth %d > %d", maxsp, MAX_STACK); return too_deep; }
     if (sp != 1) { TG_SET_ERR("expr does not reduce to one value"); return TG_ERR_INVALID_ARG; }
+    /* an item is data, not an operation: the length limit counts the rest */
+    if (n_ops > 128) { TG_SET_ERR("expression too long (>128 insts)"); return TG_ERR_UNSUPPORTED; }
     return TG_OK;
+}
+
+extern "C" tg_status tg_expr_check(const tg_expr* e)
+{
+    if (!e) { TG_SET_ERR("null arg"); return TG_ERR_INVALID_ARG; }
+    return check_expr_depth(e);
 }
 
 extern "C" tg_status tg_filter_project_create_df(tg_session* s,
@@ -1283,7 +1378,7 @@ extern "C" tg_status tg_filter_run(tg_session* s, const tg_expr* filter, const t
         return TG_ERR_INVALID_ARG;
     }
     st = tg_compile_expr(s, filter, &prog);
-    if (st != TG_OK) return st;
+    if (st != TG_OK) { tg_free_expr(s, &prog); return st; }
     /* dictionary-aware path: single-channel predicate over a fixed-width
      * dictionary block, and no input selection (whole-page evaluation) */
     int32_t fc = -1;

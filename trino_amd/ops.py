@@ -66,38 +66,71 @@ class TgAggSpec(ctypes.Structure):
 
 (OP_COL, OP_CONST_F64, OP_CONST_I64, OP_ADD, OP_SUB, OP_MUL, OP_DIV,
  OP_LE, OP_LT, OP_GE, OP_GT, OP_EQ, OP_NE, OP_AND, OP_OR, OP_NOT,
- OP_BETWEEN, OP_IN) = range(18)
+ OP_BETWEEN, OP_IN) = range(18)         # OP_IN: reserved, rejected by the library
+(OP_IS_NULL, OP_SELECT, OP_COALESCE, OP_CONST_NULL, OP_IN_LIST,
+ OP_IN_ITEM) = range(32, 38)
 
 
 def expr(*postfix):
     """Build a TgExpr from postfix tuples: ('col', i) ('f64', v) ('i64', v)
-    or op names 'le','mul','and',..."""
+    ('null', 0 | 1) ('in', [values]) or op names 'le','mul','and',...
+
+    ('null', lane) pushes NULL in the integer (0) or double (1) lane.
+    ('in', values) pops a and pushes `a IN (values)`: BIGINT items, in any
+    order, duplicates allowed; it expands to IN_LIST plus one IN_ITEM each.
+    'is_null' pops a and pushes 1 / 0. 'coalesce' pops b, a and pushes a if
+    it is non-NULL, else b. 'select' takes otherwise, cond, then (pushed in
+    that order) and pushes `then` if cond is non-NULL and non-zero, else
+    `otherwise`: IF(c, a, b) is b, c, a, 'select'; a searched CASE is
+    else, cN, vN, 'select', ..., c1, v1, 'select'."""
     ops = {"add": OP_ADD, "sub": OP_SUB, "mul": OP_MUL, "div": OP_DIV,
            "le": OP_LE, "lt": OP_LT, "ge": OP_GE, "gt": OP_GT,
            "eq": OP_EQ, "ne": OP_NE, "and": OP_AND, "or": OP_OR,
-           "not": OP_NOT, "between": OP_BETWEEN}
-    insts = (TgExprInst * len(postfix))()
-    for i, it in enumerate(postfix):
+           "not": OP_NOT, "between": OP_BETWEEN, "is_null": OP_IS_NULL,
+           "select": OP_SELECT, "coalesce": OP_COALESCE}
+    flat = []          # (op, arg0, i64 | None, f64 | None)
+    for it in postfix:
         if isinstance(it, tuple):
             kind, v = it
             if kind == "col":
-                insts[i].op = OP_COL
-                insts[i].arg0 = v
+                flat.append((OP_COL, v, None, None))
             elif kind == "f64":
-                insts[i].op = OP_CONST_F64
-                insts[i].imm.f64 = float(v)
+                flat.append((OP_CONST_F64, 0, None, float(v)))
             elif kind == "i64":
-                insts[i].op = OP_CONST_I64
-                insts[i].imm.i64 = int(v)
+                flat.append((OP_CONST_I64, 0, int(v), None))
+            elif kind == "null":
+                flat.append((OP_CONST_NULL, int(v), None, None))
+            elif kind == "in":
+                items = [int(x) for x in v]
+                flat.append((OP_IN_LIST, len(items), None, None))
+                flat += [(OP_IN_ITEM, 0, x, None) for x in items]
             else:
                 raise ValueError(kind)
         else:
-            insts[i].op = ops[it]
+            flat.append((ops[it], 0, None, None))
+    insts = (TgExprInst * len(flat))()
+    for i, (op, arg0, i64, f64) in enumerate(flat):
+        insts[i].op = op
+        insts[i].arg0 = arg0
+        if i64 is not None:
+            insts[i].imm.i64 = i64
+        elif f64 is not None:
+            insts[i].imm.f64 = f64
     e = TgExpr()
     e.insts = insts
-    e.count = len(postfix)
+    e.count = len(flat)
     e._keepalive = insts
     return e
+
+
+_lib.tg_expr_check.restype = ctypes.c_int
+_lib.tg_expr_check.argtypes = [ctypes.POINTER(TgExpr)]
+
+
+def expr_check(e):
+    """The library's create-time validation of a program, on the host alone
+    (no session, no GPU): raises what filter_run / filter_project would."""
+    _check(_lib.tg_expr_check(ctypes.byref(e)))
 
 
 def page_from_numpy(columns, valids=None):

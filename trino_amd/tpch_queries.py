@@ -1357,15 +1357,12 @@ def q16_gpu(session, sf, part_count=None):
                                             (p_sz.value, ops.TG_INTEGER)],
                                            part_count))
     sizes = [49, 14, 23, 45, 19, 3, 36, 9]
-    in_chain = []
-    for i, v in enumerate(sizes):
-        in_chain += [("col", 3), ("i64", v), "eq"]
-        if i:
-            in_chain.append("or")
-    fexpr = ops.expr(*(in_chain +
-                       [("col", 1), ("i64", 45), "ne", "and",
-                        ("col", 2), ("i64", 65), ("i64", 69), "between",
-                        "not", "and"]))
+    # three terms of the conjunction kernel: a one-word set test (sizes span
+    # 3..49), a compare and a negated BETWEEN
+    fexpr = ops.expr(("col", 3), ("in", sizes),
+                     ("col", 1), ("i64", 45), "ne", "and",
+                     ("col", 2), ("i64", 65), ("i64", 69), "between",
+                     "not", "and")
     fp = ops.filter_project(session, fexpr,
                             [ops.expr(("col", 0)), ops.expr(("col", 1)),
                              ops.expr(("col", 2)), ops.expr(("col", 3))],
