@@ -630,6 +630,76 @@ tg_status tg_topn_create(tg_session*,
     const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
     int32_t limit, tg_operator** out);
 
+/* ---- OrderBy (operator/OrderByOperator.java): ORDER BY without LIMIT, and
+ * TopN over any channel types, VARCHAR included ----
+ * tg_order_by_create accumulates pages and emits every row, ordered, as ONE
+ * page at finish. tg_topn_create_ex is tg_topn_create with VARCHAR allowed:
+ * the first `limit` rows of what tg_order_by_create emits for the same
+ * arguments with every channel output.
+ *
+ * Ordering rules. Keys are most significant first. sort_desc[i]: 0 = ASC
+ * nulls last, 1 = DESC nulls first. Fixed-width keys follow tg_topn_create's
+ * rule exactly: NaN is the largest non-NULL value, -0.0 == 0.0. A VARCHAR key
+ * orders by unsigned bytes, lexicographically, and a proper prefix sorts
+ * first (VarcharType / Slice.compareTo):
+ *     '' < '\0' < '\0\0' < 'a' < 'a\0' < 'ab' < '\x7f' < '\x80'
+ * '' is a value, not NULL. Rows whose whole key ties KEEP INPUT ORDER (page
+ * order, then row order), through both entry points and at every row count,
+ * so outputs are reproducible bit for bit. The order always comes from the
+ * device: there is no host path and no row threshold.
+ *
+ * Output. One page at finish; no input rows (or only zero-row pages): no
+ * page, and `finished` is set. Any channel may be VARCHAR, as a key or as
+ * payload. Output offsets start at 0, and a NULL VARCHAR cell has zero
+ * length. A channel carries a validity bitmap exactly when some non-empty
+ * input page's block had one. output_channels may select a subset, reorder,
+ * or repeat a channel, and sort channels need not be output; NULL / 0 emits
+ * every channel in order. For tg_topn_create_ex a limit larger than the input
+ * emits everything.
+ *
+ * Rejected before anything is launched, TG_ERR_INVALID_ARG: a null session /
+ * types / out, n_sort < 1, a sort or output channel outside the channels,
+ * limit < 1, n_output < 0, a null array with a non-zero count, a type outside
+ * tg_type. At add_input, TG_ERR_INVALID_ARG: a page with fewer channels than
+ * declared, a fixed-width channel whose cell width differs from `types`, a
+ * VARCHAR block where a fixed-width type was declared, or the reverse. At
+ * add_input, TG_ERR_UNSUPPORTED: the bytes accumulated in one VARCHAR channel
+ * (offsets[n] per page, the bytes the block carries) exceed INT32_MAX
+ * (output offsets are int32), or the accumulated rows exceed INT32_MAX; both
+ * are host-side sums, and the refused page is not kept. The operator stays usable and closable
+ * after a rejected page.
+ *
+ * tg_topn_create, tg_window_create, tg_window_create_ex and
+ * tg_topn_ranking_create are untouched: they keep rejecting VARCHAR.
+ *
+ * TG_VAR_COPY_LANES (a power of two, 1..64) in the environment, read at each
+ * emit, overrides the lanes per row of the VARCHAR byte copy, which is
+ * otherwise chosen from the mean output length. A measurement knob: the
+ * result does not depend on it.
+ *
+ * Out of scope: VARCHAR through Window / window_ex / TopNRanking (new entry
+ * points; the string image added here is what they will use), moving the
+ * TPC-H queries' final host sorts onto this operator, collations other than
+ * bytes, paged (multi-page) output, spilling, restricting later refinement
+ * rounds of the string image to the rows that still tie. */
+tg_status tg_order_by_create(tg_session*,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    const int32_t* output_channels, int32_t n_output,   /* NULL / 0 = every channel in order */
+    tg_operator** out);
+tg_status tg_topn_create_ex(tg_session*,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    int32_t limit, tg_operator** out);
+
+/* host-only hook for tests: *out = the chunk of bytes[0, len) in refinement
+ * round `round` of the VARCHAR sort image, i.e. bytes [8 * round, 8 * round +
+ * 8) big-endian, zero past len, through the very function the kernel runs
+ * (csrc/var_keys.h); no session, no GPU. len == 0 may pass NULL. A null out,
+ * a negative len or round: TG_ERR_INVALID_ARG. */
+tg_status tg_varchar_chunk_host(const uint8_t* bytes, int32_t len, int32_t round,
+    uint64_t* out);
+
 /* ---- Window (operator/WindowOperator.java): ranking functions and running
  * aggregates OVER (PARTITION BY ... ORDER BY ...) ----
  * Pages accumulate as in TopN. At finish the operator emits ONE page: every

@@ -15,6 +15,7 @@ struct DevBlock {
     void* data = nullptr;          /* owned device buffer */
     uint64_t* valid = nullptr;     /* packed bitmap, bit=1 valid; null = no nulls */
     int32_t* offsets = nullptr;    /* VARCHAR: n+1 offsets into data */
+    int64_t var_bytes = 0;         /* VARCHAR: offsets[n], as tg_upload_page read it */
     bool owned = true;
     bool valid_owned_override = false;   /* data owned but bitmap borrowed */
     int64_t elem_size() const

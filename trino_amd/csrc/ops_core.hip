@@ -113,6 +113,7 @@ tg_status tg_upload_page(tg_session* s, const tg_page* in, DevPage* out)
             else {
                 total_bytes = b->offsets[db->n];
             }
+            db->var_bytes = total_bytes;
             tg_status st = upload_flat(s, b->offsets, b->on_device,
                                        (db->n + 1) * 4, (void**)&db->offsets);
             if (st != TG_OK) return st;

@@ -11,6 +11,9 @@
  * is used where it lies. Below that, the sort-key channels are brought to the
  * host, a partial_sort selects the indices and they are uploaded. Either way
  * the output page is gathered on the device (gather_pages).
+ *
+ * OrderByOp, below it, is ORDER BY without LIMIT and TopN with VARCHAR
+ * channels (tg_order_by_create, tg_topn_create_ex): always the device path.
  */
 #include "dev_hash.h"
 #include "sort_keys.h"   /* the page check, order_pages, gather_pages */
@@ -210,8 +213,7 @@ extern "C" tg_status tg_topn_create(tg_session* s,
             TG_SET_ERR("topn sort channel %d outside %d channels", sort_channels[i], n_channels);
             return TG_ERR_INVALID_ARG;
         }
-    /* the output gather moves fixed-width cells only: no plan needs a VARCHAR
-     * channel through TopN yet, so it is rejected rather than mangled */
+    /* fixed-width channels only here; VARCHAR goes through tg_topn_create_ex */
     for (int i = 0; i < n_channels; i++)
         if (types[i] == TG_VARCHAR) {
             TG_SET_ERR("topn: VARCHAR channel %d is not supported", i);
@@ -225,4 +227,166 @@ extern "C" tg_status tg_topn_create(tg_session* s,
     op->limit = limit;
     *out = op;
     return TG_OK;
+}
+
+/* ---- OrderBy / TopN with VARCHAR (tg_order_by_create, tg_topn_create_ex) ----
+ * operator/OrderByOperator.java, and TopNOperator over any channel types.
+ * One operator: every accumulated row is ordered on the device (order_pages;
+ * a VARCHAR key sorts by its rank image) and the first `take`
+ * rows are gathered through output_channels (gather_pages). `limit` is absent
+ * (< 0) for OrderBy. No host path and no row threshold: whole-key ties keep
+ * input order at every row count. */
+struct OrderByOp : tg_operator {
+    const char* name = "order_by";
+    std::vector<tg_type> types;
+    std::vector<int32_t> sort_channels;
+    std::vector<int32_t> sort_desc;     /* 0 asc, 1 desc */
+    std::vector<int32_t> output_channels;
+    int64_t limit = -1;                 /* < 0: every row */
+    std::vector<DevPage> pages;
+    std::vector<int64_t> var_bytes;     /* per channel: VARCHAR bytes accumulated */
+    int64_t total_rows = 0;
+    bool emitted = false;
+
+    tg_status add_input(const tg_page* page) override
+    {
+        TG_TRY(check_page(name, page, types));
+        /* output offsets are int32 and the scans count rows in int32: sums on
+         * the host */
+        if (total_rows + page->position_count > INT32_MAX) {
+            TG_SET_ERR("%s: more than INT32_MAX rows accumulated", name);
+            return TG_ERR_UNSUPPORTED;
+        }
+        DevPage in;
+        tg_status st = tg_upload_page(s, page, &in);
+        /* the bytes a VARCHAR block carries, offsets[n], as the upload read
+         * them: no second trip to a device-resident page */
+        for (size_t c = 0; st == TG_OK && c < types.size(); c++)
+            if (types[c] == TG_VARCHAR && var_bytes[c] + in.blocks[c].var_bytes > INT32_MAX) {
+                TG_SET_ERR("%s: VARCHAR channel %zu accumulates more than INT32_MAX bytes",
+                           name, c);
+                st = TG_ERR_UNSUPPORTED;
+            }
+        if (st != TG_OK) {
+            tg_free_page(s, &in);
+            return st;
+        }
+        for (size_t c = 0; c < types.size(); c++) var_bytes[c] += in.blocks[c].var_bytes;
+        total_rows += in.n;
+        pages.emplace_back(std::move(in));
+        return TG_OK;
+    }
+
+    /* the order, then the output gather, then one stream sync */
+    tg_status emit_into(PoolScratch& ps, int64_t take, DevPage* outp)
+    {
+        std::vector<std::pair<int32_t, int32_t>> keys;
+        for (size_t j = 0; j < sort_channels.size(); j++)
+            keys.emplace_back(sort_channels[j], sort_desc[j]);
+        int64_t* d_idx = nullptr;
+        TG_TRY(ps.alloc(&d_idx, total_rows * 8));
+        TG_TRY(order_pages(s, ps, pages, total_rows, keys, d_idx, nullptr));
+        TG_TRY(gather_pages(s, pages, types, d_idx, take, outp, &output_channels));
+        TG_HIP_CHECK(hipStreamSynchronize(s->stream));
+        return TG_OK;
+    }
+
+    tg_status emit()
+    {
+        if (total_rows) {
+            DevPage outp;
+            tg_status st;
+            {
+                PoolScratch ps(s);
+                st = emit_into(ps, limit < 0 ? total_rows : std::min(limit, total_rows), &outp);
+            }
+            if (st != TG_OK) {
+                tg_free_page(s, &outp);
+                return st;
+            }
+            stage_output(std::move(outp));
+        }
+        for (auto& p : pages) tg_free_page(s, &p);
+        pages.clear();
+        return TG_OK;
+    }
+
+    tg_status get_output(tg_page* out, int* finished) override
+    {
+        if (input_finished && !emitted) {
+            emitted = true;
+            tg_status st = emit();
+            if (st != TG_OK) return st;
+        }
+        emit_staged(out, finished);
+        return TG_OK;
+    }
+
+    ~OrderByOp() override
+    {
+        for (auto& p : pages) tg_free_page(s, &p);
+        for (auto& p : out_pages_) tg_free_page(s, &p);
+    }
+};
+
+/* every check of both entry points; limit < 0 = OrderBy */
+static tg_status order_by_create(const char* name, tg_session* s,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    const int32_t* output_channels, int32_t n_output, int64_t limit, tg_operator** out)
+{
+    if (!s || !types || !out || n_channels < 1 || n_sort < 1 || n_output < 0 ||
+        !sort_channels || !sort_desc || (!output_channels && n_output > 0)) {
+        TG_SET_ERR("invalid %s spec", name);
+        return TG_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n_channels; i++)
+        if (types[i] < TG_BIGINT || types[i] > TG_VARCHAR) {
+            TG_SET_ERR("%s: unknown type %d of channel %d", name, types[i], i);
+            return TG_ERR_INVALID_ARG;
+        }
+    for (int i = 0; i < n_sort; i++)
+        if (sort_channels[i] < 0 || sort_channels[i] >= n_channels) {
+            TG_SET_ERR("%s sort channel %d outside %d channels", name, sort_channels[i], n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+    for (int i = 0; i < n_output; i++)
+        if (output_channels[i] < 0 || output_channels[i] >= n_channels) {
+            TG_SET_ERR("%s output channel %d outside %d channels", name, output_channels[i], n_channels);
+            return TG_ERR_INVALID_ARG;
+        }
+    auto* op = new OrderByOp();
+    op->s = s;
+    op->name = name;
+    for (int i = 0; i < n_channels; i++) op->types.push_back((tg_type)types[i]);
+    op->sort_channels.assign(sort_channels, sort_channels + n_sort);
+    for (int i = 0; i < n_sort; i++) op->sort_desc.push_back(sort_desc[i] ? 1 : 0);
+    if (n_output) op->output_channels.assign(output_channels, output_channels + n_output);
+    else for (int i = 0; i < n_channels; i++) op->output_channels.push_back(i);
+    op->var_bytes.assign(n_channels, 0);
+    op->limit = limit;
+    *out = op;
+    return TG_OK;
+}
+
+extern "C" tg_status tg_order_by_create(tg_session* s,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    const int32_t* output_channels, int32_t n_output, tg_operator** out)
+{
+    return order_by_create("order_by", s, types, n_channels, sort_channels, sort_desc, n_sort,
+                           output_channels, n_output, -1, out);
+}
+
+extern "C" tg_status tg_topn_create_ex(tg_session* s,
+    const int32_t* types, int32_t n_channels,
+    const int32_t* sort_channels, const int32_t* sort_desc, int32_t n_sort,
+    int32_t limit, tg_operator** out)
+{
+    if (limit < 1) {
+        TG_SET_ERR("topn_ex: limit %d < 1", limit);
+        return TG_ERR_INVALID_ARG;
+    }
+    return order_by_create("topn_ex", s, types, n_channels, sort_channels, sort_desc, n_sort,
+                           nullptr, 0, limit, out);
 }

@@ -39,7 +39,7 @@ __device__ static inline uint64_t topn_sortable(const void* data, int32_t type, 
 
 /* key images of one ordering channel, indexed by flat input row */
 struct SortKeyImages {
-    const uint64_t* kf;   /* topn_sortable image (0 where NULL) */
+    const uint64_t* kf;   /* topn_sortable image, or a VARCHAR channel's rank (0 where NULL) */
     const uint64_t* nf;   /* null-pass bit; nullptr when the channel has no NULLs */
 };
 
@@ -48,9 +48,16 @@ struct SortKeyImages {
 tg_status check_fixed_width_page(const char* op, const tg_page* page,
                                  const std::vector<tg_type>& types);
 
+/* the same for operators that take VARCHAR: a VARCHAR block exactly where
+ * `types` declares one, every other cell as wide as declared */
+tg_status check_page(const char* op, const tg_page* page, const std::vector<tg_type>& types);
+
 /* order the total_rows rows of `pages` by (channel, desc) keys, most
  * significant first, into d_perm[total_rows] (flat row indices; ASC = nulls
- * last, DESC = nulls first; whole-key ties keep input order). Temporaries
+ * last, DESC = nulls first; whole-key ties keep input order). The image of a
+ * VARCHAR key channel is the row's dense rank among the channel's non-NULL
+ * strings in unsigned byte order (a proper prefix first), so
+ * image equality is grouping equality for every type. Temporaries
  * come from `ps`; with `images` the per-key images are handed back, alive as
  * long as `ps`. */
 tg_status order_pages(tg_session* s, PoolScratch& ps, const std::vector<DevPage>& pages,
@@ -58,9 +65,14 @@ tg_status order_pages(tg_session* s, PoolScratch& ps, const std::vector<DevPage>
                       const std::vector<std::pair<int32_t, int32_t>>& keys,
                       int64_t* d_perm, std::vector<SortKeyImages>* images);
 
-/* gather channels [0, types.size()) of `pages` through the flat row indices
- * d_idx[take] into outp, validity included. Asynchronous on the session
- * stream; on error outp holds what was allocated, for tg_free_page. */
+/* gather channels [0, types.size()) of `pages`, or the channels listed in
+ * out_channels (any subset, order or repetition), through the flat row
+ * indices d_idx[take] into outp, validity included. A VARCHAR channel goes
+ * through a lengths pass, a scan to offsets starting at 0 and a byte copy per
+ * source page; a NULL VARCHAR cell has zero length. Asynchronous on the
+ * session stream but for the one read of a VARCHAR channel's byte total; on
+ * error outp holds what was allocated, for tg_free_page. */
 tg_status gather_pages(tg_session* s, const std::vector<DevPage>& pages,
                        const std::vector<tg_type>& types, const int64_t* d_idx,
-                       int64_t take, DevPage* outp);
+                       int64_t take, DevPage* outp,
+                       const std::vector<int32_t>* out_channels = nullptr);

@@ -498,6 +498,61 @@ def topn(session, types, sort_channels, sort_desc, limit):
     return op
 
 
+_lib.tg_order_by_create.restype = ctypes.c_int
+_lib.tg_order_by_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+_lib.tg_topn_create_ex.restype = ctypes.c_int
+_lib.tg_topn_create_ex.argtypes = _lib.tg_topn_create.argtypes
+_lib.tg_varchar_chunk_host.restype = ctypes.c_int
+_lib.tg_varchar_chunk_host.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_void_p]
+
+
+def order_by(session, types, sort_channels, sort_desc, output_channels=None):
+    """OrderBy operator (operator/OrderByOperator analog): every input row,
+    ordered, as one page at finish. Any channel may be TG_VARCHAR, as a key
+    (unsigned byte order, a proper prefix first) or as payload; whole-key
+    ties keep input order. output_channels selects, reorders or repeats
+    channels; None emits every channel in order."""
+    h = ctypes.c_void_p()
+    ty = _i32arr(types)
+    sc = _i32arr(sort_channels)
+    sd = _i32arr(sort_desc)
+    oc = _i32arr([] if output_channels is None else output_channels)
+    _check(_lib.tg_order_by_create(
+        session._h, ty.ctypes.data, len(ty), sc.ctypes.data, sd.ctypes.data, len(sc),
+        oc.ctypes.data if len(oc) else None, len(oc), ctypes.byref(h)))
+    op = Operator(session, h)
+    op._keep = (ty, sc, sd, oc)
+    return op
+
+
+def topn_ex(session, types, sort_channels, sort_desc, limit):
+    """TopN with VARCHAR channels allowed: the first `limit` rows of order_by
+    over the same arguments, always ordered on the device (ties keep input
+    order, unlike topn)."""
+    h = ctypes.c_void_p()
+    ty = _i32arr(types)
+    sc = _i32arr(sort_channels)
+    sd = _i32arr(sort_desc)
+    _check(_lib.tg_topn_create_ex(session._h, ty.ctypes.data, len(ty), sc.ctypes.data,
+                                  sd.ctypes.data, len(sc), limit, ctypes.byref(h)))
+    op = Operator(session, h)
+    op._keep = (ty, sc, sd)
+    return op
+
+
+def varchar_chunk_host(data, round_):
+    """The chunk of the bytes `data` in refinement round `round_` of the
+    VARCHAR sort image, through the function the kernel runs (no GPU)."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    out = ctypes.c_uint64()
+    _check(_lib.tg_varchar_chunk_host(buf.ctypes.data if len(buf) else None, len(buf),
+                                      round_, ctypes.byref(out)))
+    return out.value
+
+
 (WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT_STAR, WIN_COUNT_COL,
  WIN_SUM_I64, WIN_MIN_I64, WIN_MAX_I64) = range(8)
 WIN_FRAME_RANGE, WIN_FRAME_ROWS, WIN_FRAME_PARTITION = range(3)
